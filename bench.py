@@ -18,10 +18,15 @@ SUT serves it, all inside the timed region:
   * the responses of all ranks streamed to rank 0's host per completed batch (rnnt_amd.dist.ResponseStream).
 Weak scaling: the query grows with the GPU count (--query per GPU), one query served by all.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 ``--gpus N`` without a torchrun environment starts the N ranks itself (torch.distributed.run as a
 child process, before anything touches HIP), so both command lines measure N GPUs.
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step and
+the roofline of the timed steps' own HIP events).  ``--full`` adds what takes runs of its own: the
+isolated pass behind roofline.isolated, the CPU baseline with its parity spot check, and the WER
+sample.  ``--dump-outputs DIR`` writes the responses of the last timed step as .npy arrays.
 """
 import argparse
 import json
@@ -73,8 +78,14 @@ def parse():
     ap.add_argument("--batch-order", default=None,
                     help="development: this rank's batches in another order, a permutation of their indices "
                          "(e.g. 0,5,1,4,2,3; default: longest first)")
-    ap.add_argument("--cpu-sample", type=int, default=256, help="utterances timed on the CPU restatement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the isolated pass (roofline.isolated), the CPU baseline with "
+                         "its parity spot check and the WER sample; a plain run does none of them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's responses to DIR as .npy arrays (dump_outputs)")
+    ap.add_argument("--cpu-sample", type=int, default=256, help="--full: utterances timed on the CPU restatement")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline, the parity spot check and the WER sample")
     ap.add_argument("--wav", action="store_true",
                     help="WAV=true path (launch_sut.sh:53-55): the QSL holds 16 kHz audio and every batch runs the "
                          "GPU featurizer (FilterbankFeatures.forward) inside the timed region")
@@ -175,8 +186,11 @@ def mock_main(args):
         assert len(got[0]) == query and len(np.unique(got[0])) == query, "gathered responses do not cover the query"
         if args.dump_responses:
             np.savez_compressed(args.dump_responses, ids=got[0], lens=got[1], toks=got[2])
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *got)
         print(json.dumps({"metric": METRIC, "value": None, "unit": "utterances/s", "n_gpus": world,
-                          "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+                          "steps": args.steps, "warmup": args.warmup, "queries_issued": qno[0],
+                          "ms_per_step": round(elapsed / args.steps * 1e3, 3),
                           "rows_per_s_gathered": round(query * args.steps / elapsed, 1),
                           "tokens_per_query": int(got[1].sum()),
                           "data": "mock: no engine, stand-in responses (launcher / sharding check, not a measurement)",
@@ -382,11 +396,41 @@ def responses_dict(ids, lens, toks):
     return out
 
 
+DUMP_ROWS = 65536  # token rows written by --dump-outputs (a seeded sample of a larger query)
+DUMP_TOKEN_BYTES = 48 << 20  # float32 tokens written at most (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, ids, lens, toks, seed=4):
+    """--dump-outputs: the responses of the last timed step (what QuerySamplesComplete would carry), as
+    arrays (float32; the ids float64) in the order of the sample ids, so that two runs compare element for element
+    whatever order the batches completed in:
+      res_len.npy    tokens per sample, every sample of the query, by ascending id;
+      token_ids.npy  the samples whose tokens are written: all of them, or a seeded sample of
+                     DUMP_ROWS ids (chosen from the ids alone, so it is the same in every run);
+      tokens.npy     those samples' token rows, concatenated in token_ids order."""
+    os.makedirs(path, exist_ok=True)
+    ids, lens, toks = np.asarray(ids), np.asarray(lens), np.asarray(toks)
+    off = np.concatenate([[0], np.cumsum(lens, dtype=np.int64)])
+    order = np.argsort(ids, kind="stable")
+    if len(order) > DUMP_ROWS:
+        pick = np.sort(np.random.default_rng(seed).permutation(len(order))[:DUMP_ROWS])
+    else:
+        pick = np.arange(len(order))
+    rows = order[pick]
+    fits = np.searchsorted(np.cumsum(lens[rows], dtype=np.int64) * 4, DUMP_TOKEN_BYTES, side="right")
+    rows = rows[:fits]
+    np.save(os.path.join(path, "res_len.npy"), lens[order].astype(np.float32))
+    np.save(os.path.join(path, "token_ids.npy"), ids[rows].astype(np.float64))
+    np.save(os.path.join(path, "tokens.npy"),
+            np.concatenate([toks[off[r]: off[r + 1]] for r in rows] or [np.zeros(0)]).astype(np.float32))
+
+
 def summarize(args, world, query, elapsed_max, st, iso, lengths, mine, got, my_emitted, sizes):
     """The JSON line of a measured run (everything but the rank-0-only extras): value, roofline (this
     rank's share of the query: a rank may run no batch at all -- a query of fewer batches than ranks, or
     claims taken by faster ranks), config.  st / iso: summed rnnt_engine_get_stats of the timed steps /
-    of the isolated pass; lengths: the QSL's lengths; mine: this rank's (ids, qsl indices) batches."""
+    of the isolated pass (None: a plain run has none); lengths: the QSL's lengths; mine: this rank's
+    (ids, qsl indices) batches."""
     value = query * args.steps / elapsed_max
     # this rank's share (a rank may run no batch: a query of fewer batches than ranks, or claims
     # taken by faster ranks)
@@ -395,7 +439,7 @@ def summarize(args, world, query, elapsed_max, st, iso, lengths, mine, got, my_e
     enc_ops = float(sum(encoder_ops(int(l)) for l in qlens))  # SURVEY 8d E(T), valid frames
     emitted = int(got[1].sum()) if got is not None else 0  # whole query (rank 0 holds the gathered responses)
     achieved = enc_ops * args.steps / (st["encode_ms"] * 1e-3) / 1e12 if st["encode_ms"] > 0 else 0.0
-    achieved_iso = enc_ops / (iso["encode_ms"] * 1e-3) / 1e12 if iso["encode_ms"] > 0 else 0.0
+    achieved_iso = enc_ops / (iso["encode_ms"] * 1e-3) / 1e12 if iso and iso["encode_ms"] > 0 else 0.0
     traffic, traffic_src = None, None
     if os.path.exists(args.traffic_json):
         try:
@@ -406,7 +450,7 @@ def summarize(args, world, query, elapsed_max, st, iso, lengths, mine, got, my_e
     # decode work: D = (T' + U) * 4,682,752 bf16 ops per utterance (this rank's share)
     dec_ops = float(enc_frames + my_emitted) * DECODE_OPS_PER_STEP
     dec_ms = (st["greedy_ms"] + st["joint_trans_ms"]) / args.steps
-    dec_ms_iso = iso["greedy_ms"] + iso["joint_trans_ms"]
+    dec_ms_iso = iso["greedy_ms"] + iso["joint_trans_ms"] if iso else 0.0
     dec_ach = dec_ops / (dec_ms * 1e-3) / 1e12 if dec_ms > 0 else 0.0
     dec_ach_iso = dec_ops / (dec_ms_iso * 1e-3) / 1e12 if dec_ms_iso > 0 else 0.0
     ticks_q = st["step_launches"] / args.steps
@@ -429,14 +473,15 @@ def summarize(args, world, query, elapsed_max, st, iso, lengths, mine, got, my_e
         "decode": {"kernels": "joint_trans_gemm_kernel + dec_pred/g/joint step kernels (bf16 MFMA)",
                    "ops_per_query": dec_ops, "achieved": round(dec_ach, 2), "peak": BF16_DENSE_PEAK_TFLOPS,
                    "unit": "TFLOP/s", "frac": round(dec_ach / BF16_DENSE_PEAK_TFLOPS, 4),
-                   "isolated_achieved": round(dec_ach_iso, 2),
-                   "isolated_frac": round(dec_ach_iso / BF16_DENSE_PEAK_TFLOPS, 4),
                    "note": "latency-bound lock-step greedy loop; time = joint_trans + greedy event time"},
-        "isolated": {"achieved": round(achieved_iso, 2), "frac": round(achieved_iso / INT8_DENSE_PEAK_TOPS, 4),
-                     "encode_ms_per_query": round(iso["encode_ms"], 3),
-                     "greedy_ms_per_query": round(iso["greedy_ms"], 3),
-                     "note": "untimed pass, this rank's batches back to back on one engine (no overlap)"},
     }
+    if iso:  # --full
+        roofline["decode"].update(isolated_achieved=round(dec_ach_iso, 2),
+                                  isolated_frac=round(dec_ach_iso / BF16_DENSE_PEAK_TFLOPS, 4))
+        roofline["isolated"] = {"achieved": round(achieved_iso, 2), "frac": round(achieved_iso / INT8_DENSE_PEAK_TOPS, 4),
+                                "encode_ms_per_query": round(iso["encode_ms"], 3),
+                                "greedy_ms_per_query": round(iso["greedy_ms"], 3),
+                                "note": "untimed pass, this rank's batches back to back on one engine (no overlap)"}
     out = {
         "metric": METRIC, "value": round(value, 2), "unit": "utterances/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed_max / args.steps * 1e3, 3),
@@ -534,12 +579,14 @@ def main():
     sts = [e.stats(reset=True) for e in engines]
     st = {k: sum(x[k] for x in sts) for k in sts[0]}
     batch_engine = [e for e in sut.batch_engine if e is not None]  # aligned with `mine` (the batches this rank ran)
-    # isolated pass (untimed): this rank's batches once more on one engine, back to back, so the
-    # encoder's event time is not shared with an overlapping decode
-    iso_sut = OfflineSUT([engines[0]], qsl)
-    iso_sut.issue_batches(mine)
-    iso_sut.take_completed()
-    iso = engines[0].stats(reset=True)
+    iso_sut, iso = None, None
+    if args.full:
+        # isolated pass (untimed): this rank's batches once more on one engine, back to back, so the
+        # encoder's event time is not shared with an overlapping decode
+        iso_sut = OfflineSUT([engines[0]], qsl)
+        iso_sut.issue_batches(mine)
+        iso_sut.take_completed()
+        iso = engines[0].stats(reset=True)
     for e in engines:
         e.set_profiling(False)
     out = summarize(args, world, query, elapsed_max, st, iso, qsl.lengths, mine, got, my_emitted, sizes)
@@ -547,10 +594,12 @@ def main():
         assert len(got[0]) == query and len(np.unique(got[0])) == query, "gathered responses do not cover the query"
         if args.dump_responses:
             np.savez_compressed(args.dump_responses, ids=got[0], lens=got[1], toks=got[2])
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *got)
     if args.share_device:
         out["rehearsal"] = (f"{world} ranks share cuda:0 (gloo control plane): multi-process path check, not a "
                             "measurement")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.wav:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.wav:
         resp = responses_dict(*got)
         cb = cpu_baseline(pm, qsl, mine, batch_engine, resp, args.cpu_sample, args.inflight)
         out["cpu_baseline"] = {"value": round(cb["value"], 3), "unit": "utterances/s", "cores": cb["cores"],

@@ -88,12 +88,53 @@ def test_dumped_responses_equal_across_rank_counts(tmp_path):
     assert out.returncode == 1 and json.loads(out.stdout)["mismatched_rows"] == 1
 
 
+def test_dump_outputs_repeat_and_match_the_responses(tmp_path):
+    """--dump-outputs on the mock path: float32 .npy files of the last timed step, identical from run
+    to run, across step counts and across rank counts (rows by ascending sample id); the line counts the
+    queries the run issued (warmup + --steps of them); the ids are float64, the rest float32; and the
+    files hold what --dump-responses gathered."""
+    import numpy as np
+
+    def run(ranks, query, name, steps):
+        d = tmp_path / name
+        out = subprocess.run([sys.executable, BENCH, "--gpus", str(ranks), "--mock", "--steps", str(steps), "--warmup",
+                              "0", "--query", str(query), "--batch", "256", "--dump-outputs", str(d),
+                              "--dump-responses", str(tmp_path / f"{name}.npz")],
+                             capture_output=True, text=True, timeout=300, env=_env())
+        assert out.returncode == 0, out.stderr[-2000:]
+        rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert rec["steps"] == steps and rec["queries_issued"] == steps and rec["ms_per_step"] > 0
+        return {k: np.load(d / f"{k}.npy") for k in ("res_len", "token_ids", "tokens")}
+
+    a, b, c = run(1, 1536, "a", 1), run(1, 1536, "b", 2), run(2, 768, "c", 1)
+    for k, v in a.items():
+        assert v.dtype == (np.float64 if k == "token_ids" else np.float32), k
+        assert np.array_equal(v, b[k]) and np.array_equal(v, c[k]), k
+    z = np.load(tmp_path / "a.npz")
+    order = np.argsort(z["ids"], kind="stable")
+    assert np.array_equal(a["res_len"], z["lens"][order]) and np.array_equal(a["token_ids"], np.arange(1536))
+    off = np.concatenate([[0], np.cumsum(z["lens"])])
+    assert np.array_equal(a["tokens"], np.concatenate([z["toks"][off[r]: off[r + 1]] for r in order]))
+
+
 def test_eight_ranks_gather_keeps_up_at_full_volume():
     """bench.py's 8-rank data path at the default query (300000 samples per rank,
     6144-row batches, dynamic claims) with stand-in responses of the timed workload's volume (~64
     tokens per sample): rank 0's ResponseStream receives all 2.4M rows, and the whole step -- sort,
     claims, the stand-ins and the streamed gather -- runs faster than 8 GPUs produce rows
-    (8 x 121k samples/s, BENCH_r05), so the gather cannot bound an 8-GPU step."""
+    (8 x 121k samples/s, BENCH_r05), so the gather cannot bound an 8-GPU step.
+
+    The eight ranks and rank 0's receiver need CPUs to run on: an 8-GPU host grants each rank several,
+    and the bound is out of reach where all of them share one or two (one CPU sustains about 0.6-0.7M
+    rows/s of this step, two about 1.4M).  Half a CPU per rank is the least this test takes as such a
+    host: below 4 usable CPUs (affinity capped by the cgroup quota, as bench.py's cpu_baseline counts
+    them) it skips before starting anything."""
+    import pytest
+    sys.path.insert(0, REPO)
+    import bench
+    cpus = len(bench.host_cpu_budget()[0])
+    if cpus < 4:
+        pytest.skip(f"needs 4 CPUs for the 8 ranks, found {cpus}")
     out = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--mock", "--steps", "2", "--warmup", "1"],
                          capture_output=True, text=True, timeout=600, env=_env())
     assert out.returncode == 0, out.stderr[-2000:]

@@ -42,3 +42,67 @@ def test_share_work_counted(monkeypatch):
     assert out["roofline"]["achieved"] == round(ops * 2 / 0.1 / 1e12, 2)
     assert out["config"]["encoder_frames_per_query_rank0"] == sum(encoder_frames(int(v)) for v in lengths)
     assert out["config"]["emitted_symbols_per_query"] == 9
+
+
+def test_plain_run_has_no_isolated_figures(monkeypatch):
+    """A plain run skips the isolated pass (iso None): the line keeps the timed steps' roofline and
+    carries no isolated figure; --full (iso given) reports them as before."""
+    args = _args(monkeypatch)
+    assert not args.full and args.dump_outputs is None
+    lengths = np.array([500, 300, 120], np.int32)
+    mine = [(np.array([0, 1, 2]), np.array([0, 1, 2]))]
+    got = (np.array([0, 1, 2]), np.array([5, 3, 1], np.int32), np.zeros(9, np.int32))
+    plain = bench.summarize(args, 1, 3, 0.5, _stats(100.0, 40.0, 4.0, 1000), None, lengths, mine, got, 9, None)
+    json.dumps(plain)
+    assert "isolated" not in plain["roofline"] and "isolated_frac" not in plain["roofline"]["decode"]
+    full = bench.summarize(_args(monkeypatch, "--full"), 1, 3, 0.5, _stats(100.0, 40.0, 4.0, 1000),
+                           _stats(40.0, 20.0, 2.0, 500), lengths, mine, got, 9, None)
+    assert full["roofline"]["isolated"]["encode_ms_per_query"] == 40.0 and "isolated_frac" in full["roofline"]["decode"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert plain[k] == full[k]
+    assert plain["ms_per_step"] == 250.0 and plain["roofline"]["achieved"] == full["roofline"]["achieved"]
+
+
+def _responses(n, seed):
+    rng = np.random.default_rng(seed)
+    lens = rng.integers(0, 9, n).astype(np.int32)
+    rows = [rng.integers(0, 29, int(l)).astype(np.int32) for l in lens]
+    return np.arange(n, dtype=np.int64), lens, rows
+
+
+def _load(d):
+    return {k: np.load(d / f"{k}.npy") for k in ("res_len", "token_ids", "tokens")}
+
+
+def test_dump_outputs_is_independent_of_completion_order(tmp_path):
+    """The same responses gathered in another batch order give the same files, rows by ascending id."""
+    ids, lens, rows = _responses(300, 1)
+    perm = np.random.default_rng(2).permutation(300)
+    bench.dump_outputs(str(tmp_path / "a"), ids, lens, np.concatenate(rows))
+    bench.dump_outputs(str(tmp_path / "b"), ids[perm], lens[perm], np.concatenate([rows[i] for i in perm]))
+    a, b = _load(tmp_path / "a"), _load(tmp_path / "b")
+    for k in a:
+        assert a[k].dtype == (np.float64 if k == "token_ids" else np.float32) and np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a["res_len"], lens) and np.array_equal(a["token_ids"], ids)
+    assert np.array_equal(a["tokens"], np.concatenate(rows))
+
+
+def test_dump_outputs_samples_a_large_query(tmp_path, monkeypatch):
+    """Past DUMP_ROWS samples the token rows are a sample fixed by the ids alone; past DUMP_TOKEN_BYTES
+    the sample is cut at a whole row."""
+    monkeypatch.setattr(bench, "DUMP_ROWS", 64)
+    ids, lens, rows = _responses(300, 3)
+    bench.dump_outputs(str(tmp_path / "a"), ids, lens, np.concatenate(rows))
+    a = _load(tmp_path / "a")
+    assert len(a["res_len"]) == 300 and len(a["token_ids"]) == 64 and np.all(np.diff(a["token_ids"]) > 0)
+    picked = a["token_ids"].astype(np.int64)
+    assert np.array_equal(a["tokens"], np.concatenate([rows[i] for i in picked]))
+    other = [(r + 1) % 29 for r in rows]  # other tokens, same ids: the same sample
+    bench.dump_outputs(str(tmp_path / "b"), ids, lens, np.concatenate(other))
+    assert np.array_equal(_load(tmp_path / "b")["token_ids"], a["token_ids"])
+    monkeypatch.setattr(bench, "DUMP_TOKEN_BYTES", 4 * 40)
+    bench.dump_outputs(str(tmp_path / "c"), ids, lens, np.concatenate(rows))
+    c = _load(tmp_path / "c")
+    kept = c["token_ids"].astype(np.int64)
+    assert 0 < len(kept) < 64 and np.array_equal(kept, picked[:len(kept)]) and len(c["tokens"]) <= 40
+    assert np.array_equal(c["tokens"], np.concatenate([rows[i] for i in kept]))

@@ -2,13 +2,13 @@
 # One parameterised runner for GPU-box passes (gpurun -- 'bash tools/gpu.sh <task> ...').  Every GPU
 # step has its own time limit, the chain stops at the first failure, outputs go under $OUT.
 #
-#   check                  smoke, then the -m gpu suite, then one bench line      (NO_TESTS / NO_BENCH skip)
+#   check                  smoke, then the -m gpu suite, then one bench --full line (NO_TESTS / NO_BENCH skip)
 #   ab  V1 V2 ...          end-to-end bench lines over variants, alternating ROUNDS times
 #   decab V1 V2 ...        isolated decode of the bench query (tools/bench_decode.py) over variants
 #   kernels                encoder layer-step microbenchmarks (tools/bench_kernels.py)
 #   profile                kernel-trace stats of the bench + separate PMC passes (summaries in $OUT/summary)
 #   multirank              2 / 3 ranks on one GPU (gloo, --share-device) vs one rank, responses compared
-#   timeline               kernel trace of warmup + one timed query: per-batch encode / decode spans (trace_query.py)
+#   timeline               kernel trace of warmup + one timed query + the isolated pass: per-batch encode / decode spans (trace_query.py)
 #
 # A variant is NAME[:VAR=VAL[,VAR=VAL...]]: NAME "main" is the shipped library, any other NAME loads
 # build_dev/lib_NAME.so (RNNT_MI355X_LIB); the VAR=VAL pairs are set in that run's environment.
@@ -45,7 +45,7 @@ check)
     tail -3 $OUT/pytest_gpu.log
   fi
   if [ -z "$NO_BENCH" ]; then
-    timeout -k 10 600 python -u bench.py --steps $STEPS --warmup 2 ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err \
+    timeout -k 10 600 python -u bench.py --full --steps $STEPS --warmup 2 ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err \
       || die "bench rc=$?" $OUT/bench.err
     cat $OUT/bench.json
   fi
@@ -54,7 +54,7 @@ ab)
   for r in $(seq 1 ${ROUNDS:-2}); do
     for v in "$@"; do
       tag=$(echo "$v" | tr ':,=/' '____')
-      run_variant "$v" timeout -k 10 300 python3 -u bench.py --steps $STEPS --warmup 2 --no-cpu-baseline ${BENCH_ARGS} \
+      run_variant "$v" timeout -k 10 300 python3 -u bench.py --full --steps $STEPS --warmup 2 --no-cpu-baseline ${BENCH_ARGS} \
         > $OUT/bench_${tag}_$r.json 2> $OUT/bench_${tag}_$r.err || die "$v rc=$?" $OUT/bench_${tag}_$r.err
       python3 -c "import json; d=json.load(open('$OUT/bench_${tag}_$r.json')); r=d['roofline']; print('$v', d['value'], r['encode_ms_per_query'], r['greedy_ms_per_query'], r['isolated']['encode_ms_per_query'], r['isolated']['greedy_ms_per_query'])"
     done
@@ -78,7 +78,7 @@ kernels)
 profile)
   # kernel-trace stats of the default bench workload + separate PMC passes (kernel-trace only;
   # FETCH_SIZE and WRITE_SIZE in their own passes, MI355X_MICROARCH.md HBM section)
-  BENCH="python3 bench.py --steps ${PSTEPS:-1} --warmup 1 --no-cpu-baseline ${BENCH_ARGS}"
+  BENCH="python3 bench.py --full --steps ${PSTEPS:-1} --warmup 1 --no-cpu-baseline ${BENCH_ARGS}"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- $BENCH > $OUT/trace.log 2>&1 \
     || die "trace rc=$?" $OUT/trace.log
   i=0
@@ -96,7 +96,7 @@ profile)
   ;;
 timeline)
   timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o tl -- \
-    python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline ${BENCH_ARGS} > $OUT/trace.log 2>&1 || die "trace rc=$?" $OUT/trace.log
+    python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline ${BENCH_ARGS} > $OUT/trace.log 2>&1 || die "trace rc=$?" $OUT/trace.log
   python3 tools/trace_query.py $OUT/trace > $OUT/timeline.txt && cat $OUT/timeline.txt
   python3 tools/dec_overlap.py $OUT/trace > $OUT/dec_overlap.json && cat $OUT/dec_overlap.json
   [ -n "$KEEP_TRACE" ] || find $OUT/trace -name "*_kernel_trace.csv" -delete

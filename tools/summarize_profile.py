@@ -53,7 +53,7 @@ def main():
 def per_query(src, stats_csv, prefix):
     """Encoder kernel-time fraction per query from the traced bench run: the bench line (printed to
     trace.log) gives the int8 ops of one query (roofline.achieved x encode_ms_per_query) and the
-    step count; the traced run holds warmup + timed + one isolated query (bench.py), so the tick
+    step count; the traced run holds warmup + timed + one isolated query (bench.py --full), so the tick
     kernels' total time / that many queries is the kernel time per query."""
     try:
         line = [x for x in open(os.path.join(src, "trace.log")) if x.startswith('{"metric"')][-1]
@@ -71,7 +71,7 @@ def per_query(src, stats_csv, prefix):
     if not tick_ns:
         return
     t = tick_ns * 1e-9 / queries
-    out = {"queries_in_trace": queries, "note": "bench.py --warmup W --steps K traced: W + K queries + 1 isolated pass",
+    out = {"queries_in_trace": queries, "note": "bench.py --full --warmup W --steps K traced: W + K queries + 1 isolated pass",
            "int8_ops_per_query": ops, "tick_kernel_ms_per_query": round(t * 1e3, 3),
            "tick_launches_per_query": r.get("tick_launches_per_query"),
            "encoder_kernel_time_frac": round(ops / t / 5.0e15, 4), "peak_tops": 5000.0,
