@@ -65,6 +65,12 @@ __host__ __device__ constexpr int LIVE_N(int p) { return 2 * p + 1; }
 __device__ __forceinline__ int4 live_entry(int row, int slot, int added, int time, int flen, int idx) {
   return int4{row | (slot << 24) | (added << 25), time | (flen << 16), idx, 0};
 }
+__device__ __forceinline__ int live_row(const int4 e) { return entry_row(e.x); }
+__device__ __forceinline__ int live_slot(const int4 e) { return entry_slot(e.x); }
+__device__ __forceinline__ int live_added(const int4 e) { return (e.x >> 25) & 31; }
+__device__ __forceinline__ int live_time(const int4 e) { return e.y & 0xffff; }
+__device__ __forceinline__ int live_flen(const int4 e) { return (e.y >> 16) & 0xffff; }
+__device__ __forceinline__ int live_idx(const int4 e) { return e.z; }
 
 // development instrumentation (-DRNNT_DEV_STAMPS, tools/build_variants.sh stamps): thread 0 of
 // each working workgroup of the step kernels records s_memrealtime (100 MHz) at kernel start,
@@ -409,6 +415,88 @@ template <bool PS>
 inline void st_b128(void* p, uint4 v) { *(uint4*)p = v; }
 #endif
 
+// ---- pieces shared by the big-tile bodies (dec_pred_body, dec_g_body) and the co-resident layer-1 body
+// (dec_l1_slim_body): the emit list's tiles, the row staging and the LSTM cell.
+//
+// The emit list as one workgroup walks it: row tiles gxy.y, gxy.y + gxy.ny, ... of RT entries, staged
+// in the caller's LDS (ents_all: NK = THREADS / RT tiles).  begin() loads the entries of the
+// workgroup's first NK tiles beside the list length (one memory round trip for all of them; indices
+// past Npad -- XCD rounding, long strides -- are guarded) and says whether the workgroup has a tile
+// at all; fetch() hands out the it-th tile's entries, reloading them past the prefetched tiles (that
+// LDS slot's tile is done by then).  The caller's lds_barrier follows fetch().  check_bit: the
+// caller's dec_ok bit of the reload's bound.
+template <int THREADS, int RT>
+struct EmitTiles {
+  static constexpr int NK = THREADS / RT;
+  const int* list;
+  int (*ents_all)[RT];
+  int cnt, ntiles;
+  __device__ __forceinline__ bool begin(const DecArgs& a, int parity, const GridXY gxy, int (*lds)[RT], int tid) {
+    list = a.s.list + parity * a.Npad;
+    ents_all = lds;
+    const int i0 = (gxy.y + (tid / RT) * gxy.ny) * RT + tid % RT;
+    const int e0 = i0 < a.Npad ? list[i0] : -1;
+    cnt = a.s.count[EMIT_N(parity)];
+    ntiles = (cnt + RT - 1) / RT;
+    if (gxy.y >= ntiles) return false;
+    ents_all[tid / RT][tid % RT] = i0 < cnt ? e0 : -1;
+    return true;
+  }
+  __device__ __forceinline__ int* fetch(const DecArgs& a, int rt, int it, int tid, int check_bit) const {
+    int* ents = ents_all[it % NK];
+    if (it >= NK && tid < RT)
+      ents[tid] = rt * RT + tid < cnt && dec_ok(rt * RT + tid < a.Npad, check_bit) ? list[rt * RT + tid] : -1;
+    return ents;
+  }
+};
+
+// Row staging: RT listed rows x K bf16 into LDS, 16 bytes per thread and iteration.  stage_load reads
+// this thread's entries first (one LDS round trip, not one per load) and issues every global load of
+// the tile (one memory round trip); src(entry, k) is the address of the row's k-th element, and for an
+// entry past the list end (-1) a safe cached address (row 0).  stage_store writes the tile, zeros past
+// the list end.  Between the two the caller puts a sched_barrier and its first-use weight loads, so
+// those stay behind the input loads.  The caller owns emv / xv (stage_nit elements).
+template <int THREADS, int RT, int K>
+constexpr int stage_nit() { return (RT * (K / 8) + THREADS - 1) / THREADS; }
+template <int THREADS, int RT, int K, class Src>
+__device__ __forceinline__ void stage_load(const int* ents, int (&emv)[stage_nit<THREADS, RT, K>()],
+                                           uint4 (&xv)[stage_nit<THREADS, RT, K>()], int tid, Src&& src) {
+  constexpr int NX = RT * (K / 8), NIT = stage_nit<THREADS, RT, K>();
+#pragma unroll
+  for (int u = 0; u < NIT; ++u) {
+    const int i = tid + THREADS * u;
+    emv[u] = (NX % THREADS == 0 || i < NX) ? ents[i / (K / 8)] : -1;
+  }
+#pragma unroll
+  for (int u = 0; u < NIT; ++u) {
+    const int i = tid + THREADS * u;
+    if (NX % THREADS == 0 || i < NX) xv[u] = *(const uint4*)src(emv[u], (i % (K / 8)) * 8);
+  }
+}
+template <int THREADS, int RT, int K, int XP>
+__device__ __forceinline__ void stage_store(uint16_t (*X)[XP], const int (&emv)[stage_nit<THREADS, RT, K>()],
+                                            const uint4 (&xv)[stage_nit<THREADS, RT, K>()], int tid) {
+  constexpr int NX = RT * (K / 8), NIT = stage_nit<THREADS, RT, K>();
+#pragma unroll
+  for (int u = 0; u < NIT; ++u) {
+    const int i = tid + THREADS * u;
+    if (NX % THREADS == 0 || i < NX) *(uint4*)&X[i / (K / 8)][(i % (K / 8)) * 8] = emv[u] >= 0 ? xv[u] : uint4{0u, 0u, 0u, 0u};
+  }
+}
+
+// The lstm_amx_bf16 cell of one unit: gate sums gs = (i, f, g, o), committed cell state cp -> the new
+// cell state (fp32) and the new h as bf16 bits (the contract rounds h where it is produced).
+struct CellOut {
+  float cn;
+  uint32_t hb;
+};
+__device__ __forceinline__ CellOut lstm_cell(const v4f gs, float cp) {
+  const float ig = det_sigmoid(gs[0]), fg = det_sigmoid(gs[1]), gg = det_tanh(gs[2]), og = det_sigmoid(gs[3]);
+  const float cn = fg * cp + ig * gg;
+  const float hh = bf_round_ftz(og * det_tanh(cn));
+  return CellOut{cn, __float_as_uint(hh) >> 16};  // hh is bf16-exact
+}
+
 // One prediction LSTM layer for the emit list's rows (see dec_pred_kernel).  The body runs one
 // launch's work: in the step kernel once, in the persistent decode once per step with the weight
 // slice kept in registers across steps (wl: loaded).  X / ents_all: the caller's LDS.
@@ -424,25 +512,14 @@ __device__ __forceinline__ void dec_pred_body(const DecArgs& a, int parity, cons
                                               uint16_t (*X)[pred_xp(LAYER)], int (*ents_all)[RT], PredRegs<LAYER>& W) {
   constexpr int PRED_THREADS = NW * 64;
   constexpr int KX = LAYER ? 2 * P : P;  // staged k: layer 1 [x | h], layer 0 [h]
-  constexpr int NK = PRED_THREADS / RT;  // row tiles whose list entries load up front
   constexpr int DEC_SUB = RT / 16;
-  const DecState& s = a.s;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, c = lane & 15;
   ST_MARK(st0);
-  const int* list = s.list + parity * a.Npad;
-  // the entries of this workgroup's first NK row tiles load beside the list length (one round
-  // trip for all of them; indices past Npad -- XCD rounding, long strides -- are guarded)
-  const int i0 = (gxy.y + (tid / RT) * gxy.ny) * RT + tid % RT;
-  const int e0 = i0 < a.Npad ? list[i0] : -1;
-  const int cnt = s.count[EMIT_N(parity)];
-  const int ntiles = (cnt + RT - 1) / RT;
-  if (gxy.y >= ntiles) return;
-  ents_all[tid / RT][tid % RT] = i0 < cnt ? e0 : -1;
+  EmitTiles<PRED_THREADS, RT> tiles;
+  if (!tiles.begin(a, parity, gxy, ents_all, tid)) return;
   const int t0 = gxy.x * (PRED_THREADS / 64) + wave;  // this wave's gate tile
-  for (int rt = gxy.y, it = 0; rt < ntiles; rt += gxy.ny, ++it) {
-    int* ents = ents_all[it % NK];
-    if (it >= NK && tid < RT)  // past the prefetched tiles (the slot's tile is done)
-      ents[tid] = rt * RT + tid < cnt && dec_ok(rt * RT + tid < a.Npad, 3) ? list[rt * RT + tid] : -1;
+  for (int rt = gxy.y, it = 0; rt < tiles.ntiles; rt += gxy.ny, ++it) {
+    const int* ents = tiles.fetch(a, rt, it, tid, 3);
     lds_barrier();
     ST_MARK(st1);
     // this lane's committed cell states (sub-tile st: row ents[16 st + c]) and, layer 0, its
@@ -458,27 +535,14 @@ __device__ __forceinline__ void dec_pred_body(const DecArgs& a, int parity, cons
     }
     // stage the listed rows' inputs as bf16: layer 0 h0 (committed slot); layer 1
     // [h0 of the candidate slot | h1 committed]
-    // every load of the tile first (one memory round trip); entries past the list end read row
-    // 0 (a safe cached address) and stage zeros
-    constexpr int NX = RT * (KX / 8), NIT = (NX + PRED_THREADS - 1) / PRED_THREADS;
+    constexpr int NIT = stage_nit<PRED_THREADS, RT, KX>();
     uint4 xv[NIT];
     int emv[NIT];
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {  // this thread's entries first: one LDS round trip, not one per load
-      const int i = tid + PRED_THREADS * u;
-      emv[u] = (NX % PRED_THREADS == 0 || i < NX) ? ents[i / (KX / 8)] : -1;
-    }
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {
-      const int i = tid + PRED_THREADS * u;
-      if (NX % PRED_THREADS == 0 || i < NX) {
-        const int k = (i % (KX / 8)) * 8, em = emv[u];
-        const int r = em >= 0 && dec_ok(entry_row(em) < a.Npad, 1) ? entry_row(em) : 0, smm = em >= 0 ? entry_slot(em) : 0;
-        const uint16_t* src = LAYER == 0 ? h_bf(a.hc, r, smm, 0) + k
-                                         : (k < P ? h_bf(a.hc, r, smm ^ 1, 0) + k : h_bf(a.hc, r, smm, 1) + k - P);
-        xv[u] = *(const uint4*)src;
-      }
-    }
+    stage_load<PRED_THREADS, RT, KX>(ents, emv, xv, tid, [&](int em, int k) __attribute__((always_inline)) {
+      const int r = em >= 0 && dec_ok(entry_row(em) < a.Npad, 1) ? entry_row(em) : 0, smm = em >= 0 ? entry_slot(em) : 0;
+      return LAYER == 0 ? h_bf(a.hc, r, smm, 0) + k
+                        : (k < P ? h_bf(a.hc, r, smm ^ 1, 0) + k : h_bf(a.hc, r, smm, 1) + k - P);
+    });
     __builtin_amdgcn_sched_barrier(0);  // keep the weight loads behind the input loads
     if (!W.wl) {
       W.wl = true;
@@ -492,14 +556,7 @@ __device__ __forceinline__ void dec_pred_body(const DecArgs& a, int parity, cons
       }
       W.bh = *(const float4*)(a.w.bhh_p[LAYER] + t0 * 16 + 4 * q);
     }
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {
-      const int i = tid + PRED_THREADS * u;
-      if (NX % PRED_THREADS == 0 || i < NX) {
-        const int m = i / (KX / 8), k = (i % (KX / 8)) * 8;
-        *(uint4*)&X[m][k] = emv[u] >= 0 ? xv[u] : uint4{0u, 0u, 0u, 0u};
-      }
-    }
+    stage_store<PRED_THREADS, RT, KX>(X, emv, xv, tid);
     lds_barrier();
     ST_MARK(st2);
     // the chains of every sub-tile (h, and x on layer 1) advance together, one k block at a
@@ -527,22 +584,18 @@ __device__ __forceinline__ void dec_pred_body(const DecArgs& a, int parity, cons
     for (int st = 0; st < DEC_SUB; ++st) {
       const int ec = ecs[st];
       const int row = ec >= 0 && dec_ok(entry_row(ec) < a.Npad, 2) ? entry_row(ec) : -1, sl = ec >= 0 ? entry_slot(ec) : 0;
-      const v4f gs = axs[st] + ahs[st];
+      const CellOut o = lstm_cell(axs[st] + ahs[st], cp[st]);
       const int u = t0 * 4 + q;
-      const float ig = det_sigmoid(gs[0]), fg = det_sigmoid(gs[1]), gg = det_tanh(gs[2]), og = det_sigmoid(gs[3]);
-      const float cn = fg * cp[st] + ig * gg;
-      const float hh = bf_round_ftz(og * det_tanh(cn));
-      const uint32_t hb = __float_as_uint(hh) >> 16;  // hh is bf16-exact
       if (PS) {
         // 4-byte write-through stores: units u (q even) and u + 1 (lane + 16, same row) in one word
-        const uint32_t hpair = __shfl_xor(hb, 16);
+        const uint32_t hpair = __shfl_xor(o.hb, 16);
         if (row >= 0) {
-          st_b32<true>(hc_part(a.hc, row, sl ^ 1, 2 + LAYER) + u, __float_as_uint(cn));
-          if ((q & 1) == 0) st_b32<true>(h_bf(a.hc, row, sl ^ 1, LAYER) + u, hb | (hpair << 16));
+          st_b32<true>(hc_part(a.hc, row, sl ^ 1, 2 + LAYER) + u, __float_as_uint(o.cn));
+          if ((q & 1) == 0) st_b32<true>(h_bf(a.hc, row, sl ^ 1, LAYER) + u, o.hb | (hpair << 16));
         }
       } else if (row >= 0) {
-        hc_part(a.hc, row, sl ^ 1, 2 + LAYER)[u] = cn;
-        h_bf(a.hc, row, sl ^ 1, LAYER)[u] = (uint16_t)hb;
+        hc_part(a.hc, row, sl ^ 1, 2 + LAYER)[u] = o.cn;
+        h_bf(a.hc, row, sl ^ 1, LAYER)[u] = (uint16_t)o.hb;
       }
     }
     lds_barrier();  // X (and this entry slot, NK tiles on) are restaged by the next tile
@@ -576,7 +629,6 @@ struct GRegs {
 template <bool PS, int RT = DEC_RT>
 __device__ __forceinline__ void dec_g_body(const DecArgs& a, int parity, const GridXY gxy, bool reset,
                                            uint16_t (*X)[GXP], int (*ents_all)[RT], GRegs& W) {
-  constexpr int NK = G_THREADS / RT;  // row tiles whose list entries load up front
   constexpr int DEC_SUB = RT / 16;
   const DecState& s = a.s;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, c = lane & 15;
@@ -585,36 +637,20 @@ __device__ __forceinline__ void dec_g_body(const DecArgs& a, int parity, const G
     st_b32<PS>(&s.count[EMIT_N(parity ^ 1)], 0u);
     st_b32<PS>(&s.count[LIVE_N(parity ^ 1)], 0u);
   }
-  const int* list = s.list + parity * a.Npad;
-  const int i0 = (gxy.y + (tid / RT) * gxy.ny) * RT + tid % RT;
-  const int e0 = i0 < a.Npad ? list[i0] : -1;
-  const int cnt = s.count[EMIT_N(parity)];
-  const int ntiles = (cnt + RT - 1) / RT;
-  if (gxy.y >= ntiles) return;
-  ents_all[tid / RT][tid % RT] = i0 < cnt ? e0 : -1;
+  EmitTiles<G_THREADS, RT> tiles;
+  if (!tiles.begin(a, parity, gxy, ents_all, tid)) return;
   const int jt = gxy.x * (G_THREADS / 64) + wave;  // this wave's column tile
-  for (int rt = gxy.y, it = 0; rt < ntiles; rt += gxy.ny, ++it) {
-    int* ents = ents_all[it % NK];
-    if (it >= NK && tid < RT) ents[tid] = rt * RT + tid < cnt && dec_ok(rt * RT + tid < a.Npad, 6) ? list[rt * RT + tid] : -1;
+  for (int rt = gxy.y, it = 0; rt < tiles.ntiles; rt += gxy.ny, ++it) {
+    const int* ents = tiles.fetch(a, rt, it, tid, 6);
     lds_barrier();
     ST_MARK(st1);
-    constexpr int NX = RT * (P / 8), NIT = (NX + G_THREADS - 1) / G_THREADS;
+    constexpr int NIT = stage_nit<G_THREADS, RT, P>();
     uint4 xv[NIT];
     int emv[NIT];
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {  // this thread's entries first (one LDS round trip)
-      const int i = tid + G_THREADS * u;
-      emv[u] = (NX % G_THREADS == 0 || i < NX) ? ents[i / (P / 8)] : -1;
-    }
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {  // every load first (one round trip); past the list end: row 0, zeros staged
-      const int i = tid + G_THREADS * u;
-      if (NX % G_THREADS == 0 || i < NX) {
-        const int k = (i % (P / 8)) * 8, em = emv[u];
-        const bool okr = em >= 0 && dec_ok(entry_row(em) < a.Npad, 4);
-        xv[u] = *(const uint4*)(h_bf(a.hc, okr ? entry_row(em) : 0, okr ? entry_slot(em) ^ 1 : 0, 1) + k);
-      }
-    }
+    stage_load<G_THREADS, RT, P>(ents, emv, xv, tid, [&](int em, int k) __attribute__((always_inline)) {  // h1 of the candidate slot
+      const bool okr = em >= 0 && dec_ok(entry_row(em) < a.Npad, 4);
+      return h_bf(a.hc, okr ? entry_row(em) : 0, okr ? entry_slot(em) ^ 1 : 0, 1) + k;
+    });
     __builtin_amdgcn_sched_barrier(0);  // keep the weight loads behind the input loads
     if (!W.wl) {
       W.wl = true;
@@ -623,14 +659,7 @@ __device__ __forceinline__ void dec_g_body(const DecArgs& a, int parity, const G
       for (int b = 0; b < P / 32; ++b) W.wv[b] = *(const uint4*)(w0 + 32 * b);
       W.b0 = *(const float4*)(a.w.bp + jt * 16 + 4 * q);
     }
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {
-      const int i = tid + G_THREADS * u;
-      if (NX % G_THREADS == 0 || i < NX) {
-        const int m = i / (P / 8), k = (i % (P / 8)) * 8;
-        *(uint4*)&X[m][k] = emv[u] >= 0 ? xv[u] : uint4{0u, 0u, 0u, 0u};
-      }
-    }
+    stage_store<G_THREADS, RT, P>(X, emv, xv, tid);
     lds_barrier();
     ST_MARK(st2);
     // every sub-tile's chain advances one k block at a time (fragment reads overlap MFMAs)
@@ -664,8 +693,12 @@ __global__ void __launch_bounds__(G_THREADS) dec_g_kernel(DecArgs a, int parity)
 
 // Co-resident step kernels (SLIM): 16-row tiles and a register cap, so a workgroup fits on a CU
 // beside a 256x256 encoder tick workgroup (147456 B of LDS, 2 waves x 200 VGPRs per SIMD: 16 KiB of
-// LDS and 112 VGPRs per SIMD left).  The same bodies, the same instruction sequence per row: identical
-// results.  While an encoder runs, the step kernels above wait for a tick workgroup to give up a CU.
+// LDS and 112 VGPRs per SIMD left).  These are what the engine launches; while an encoder runs, the
+// big-tile step kernels above wait for a tick workgroup to give up a CU.  Layer 0 and G are the
+// bodies above at 16 rows; layer 1 (dec_l1_slim_body) and the joint (dec_joint_slim_kernel) arrange
+// their chains differently and share everything else with the big-tile bodies -- EmitTiles,
+// stage_load / stage_store, lstm_cell, the joint_* helpers -- so every row sees the same instruction
+// sequence: identical results.
 constexpr int SLIM_RT = 16;
 #ifndef RNNT_EMU
 #define SLIM_BOUNDS __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56)))  // 112 on gfx950 (the attribute counts half)
@@ -689,23 +722,16 @@ enum { SLIM_H1 = 0, SLIM_X1 = 1 };
 template <int ROLE>
 __device__ __forceinline__ void dec_l1_slim_body(const DecArgs& a, int parity, const GridXY gxy, uint16_t (*X)[GXP],
                                                  int (*ents_all)[SLIM_RT]) {
-  constexpr int RT = SLIM_RT, NK = 256 / RT;
-  const DecState& s = a.s;
+  constexpr int RT = SLIM_RT;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, c = lane & 15;
-  const int* list = s.list + parity * a.Npad;
-  const int i0 = (gxy.y + (tid / RT) * gxy.ny) * RT + tid % RT;
-  const int e0 = i0 < a.Npad ? list[i0] : -1;
-  const int cnt = s.count[EMIT_N(parity)];
-  const int ntiles = (cnt + RT - 1) / RT;
-  if (gxy.y >= ntiles) return;
-  ents_all[tid / RT][tid % RT] = i0 < cnt ? e0 : -1;
+  EmitTiles<256, RT> tiles;
+  if (!tiles.begin(a, parity, gxy, ents_all, tid)) return;
   const int t0 = gxy.x * 4 + wave;  // this wave's gate tile
   uint4 wv[P / 32];
   float4 b0 = float4{0.0f, 0.0f, 0.0f, 0.0f};
   bool wl = false;
-  for (int rt = gxy.y, it = 0; rt < ntiles; rt += gxy.ny, ++it) {
-    int* ents = ents_all[it % NK];
-    if (it >= NK && tid < RT) ents[tid] = rt * RT + tid < cnt && dec_ok(rt * RT + tid < a.Npad, 6) ? list[rt * RT + tid] : -1;
+  for (int rt = gxy.y, it = 0; rt < tiles.ntiles; rt += gxy.ny, ++it) {
+    const int* ents = tiles.fetch(a, rt, it, tid, 6);
     lds_barrier();
     // this lane's row (column c of the tile) and, x chain, its cell state and h-chain sums
     int ec = ents[c];
@@ -717,24 +743,14 @@ __device__ __forceinline__ void dec_l1_slim_body(const DecArgs& a, int parity, c
       cp = hc_part(a.hc, erow, esl, 3)[t0 * 4 + q];
       ph = *(const float4*)(a.PH + (size_t)erow * PG4 + t0 * 16 + 4 * q);
     }
-    constexpr int NX = RT * (P / 8), NIT = (NX + 255) / 256;
+    constexpr int NIT = stage_nit<256, RT, P>();
     uint4 xv[NIT];
     int emv[NIT];
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {
-      const int i = tid + 256 * u;
-      emv[u] = (NX % 256 == 0 || i < NX) ? ents[i / (P / 8)] : -1;
-    }
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {  // every load first (one round trip); past the list end: row 0, zeros staged
-      const int i = tid + 256 * u;
-      if (NX % 256 == 0 || i < NX) {
-        const int k = (i % (P / 8)) * 8, em = emv[u];
-        const bool okr = em >= 0 && dec_ok(entry_row(em) < a.Npad, 1);
-        const int r = okr ? entry_row(em) : 0, sm = okr ? entry_slot(em) : 0;
-        xv[u] = *(const uint4*)((ROLE == SLIM_H1 ? h_bf(a.hc, r, sm, 1) : h_bf(a.hc, r, sm ^ 1, 0)) + k);
-      }
-    }
+    stage_load<256, RT, P>(ents, emv, xv, tid, [&](int em, int k) __attribute__((always_inline)) {  // h chain: h1 committed; x chain: h0 candidate
+      const bool okr = em >= 0 && dec_ok(entry_row(em) < a.Npad, 1);
+      const int r = okr ? entry_row(em) : 0, sm = okr ? entry_slot(em) : 0;
+      return (ROLE == SLIM_H1 ? h_bf(a.hc, r, sm, 1) : h_bf(a.hc, r, sm ^ 1, 0)) + k;
+    });
     __builtin_amdgcn_sched_barrier(0);  // keep the weight loads behind the input loads
     if (!wl) {
       wl = true;
@@ -743,14 +759,7 @@ __device__ __forceinline__ void dec_l1_slim_body(const DecArgs& a, int parity, c
       for (int b = 0; b < P / 32; ++b) wv[b] = *(const uint4*)(wr + 32 * b);
       b0 = *(const float4*)((ROLE == SLIM_H1 ? a.w.bhh_p[1] : a.w.bih_p[1]) + t0 * 16 + 4 * q);
     }
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {
-      const int i = tid + 256 * u;
-      if (NX % 256 == 0 || i < NX) {
-        const int m = i / (P / 8), k = (i % (P / 8)) * 8;
-        *(uint4*)&X[m][k] = emv[u] >= 0 ? xv[u] : uint4{0u, 0u, 0u, 0u};
-      }
-    }
+    stage_store<256, RT, P>(X, emv, xv, tid);
     lds_barrier();
     v4f acc = v4f{b0.x, b0.y, b0.z, b0.w};
 #pragma unroll
@@ -759,13 +768,10 @@ __device__ __forceinline__ void dec_l1_slim_body(const DecArgs& a, int parity, c
       if (ROLE == SLIM_H1) {
         *(v4f*)(a.PH + (size_t)erow * PG4 + t0 * 16 + 4 * q) = acc;
       } else {
-        const v4f gs = acc + v4f{ph.x, ph.y, ph.z, ph.w};
+        const CellOut o = lstm_cell(acc + v4f{ph.x, ph.y, ph.z, ph.w}, cp);
         const int u = t0 * 4 + q;
-        const float ig = det_sigmoid(gs[0]), fg = det_sigmoid(gs[1]), gg = det_tanh(gs[2]), og = det_sigmoid(gs[3]);
-        const float cn = fg * cp + ig * gg;
-        const float hh = bf_round_ftz(og * det_tanh(cn));
-        hc_part(a.hc, erow, esl ^ 1, 3)[u] = cn;
-        h_bf(a.hc, erow, esl ^ 1, 1)[u] = (uint16_t)(__float_as_uint(hh) >> 16);
+        hc_part(a.hc, erow, esl ^ 1, 3)[u] = o.cn;
+        h_bf(a.hc, erow, esl ^ 1, 1)[u] = (uint16_t)o.hb;
       }
     }
     lds_barrier();  // X and this entry slot are restaged by the next tile
@@ -807,11 +813,128 @@ constexpr int JOINT_ITERS = 2;  // 1 / 3 / 4 measured slower (DESIGN.md section 
 
 constexpr int YP = J + 16;  // +32 B: conflict-free fragment reads (see dec_pred_kernel's XP)
 constexpr int JRT = 16;  // joint rows per workgroup tile: the argmax maps 4 waves x 4 rows x 16 lanes onto it
+// ---- the joint's tile state and what both joints (dec_joint_body, dec_joint_slim_kernel) do with it.
+// The two differ only in how a wave gets its logit partials into Lp (B fragments staged in LDS vs
+// built in registers, and which chains a wave runs); the tile load, the argmax with
+// greedy_decode_update and the list publish below are one copy.
+struct JointTile {
+  float Lp[4][JRT][NLAB_PAD + 1];  // logit partials s_b of k block b: logits = ((s0 + s1) + s2) + s3
+  int rows[JRT], walking[JRT], tidx[JRT], emit_e[JRT];  // row (-1: none / finished), still walking, frame, emit entry
+  int slot_[JRT], add_[JRT], flen_[JRT], idx_[JRT];     // the rest of the row's greedy state (live_entry)
+};
+// Tile rt of the live list (lcnt entries) into T: threads < JRT, one row each.  The first tile's
+// entries come from r_first, which the caller loaded beside lcnt (one memory round trip).
+__device__ __forceinline__ void joint_load_tile(JointTile& T, const DecArgs& a, const int4* llist, int lcnt, int rt,
+                                                bool first, const int4 r_first, int tid) {
+  if (tid < JRT) {
+    const int i = rt * JRT + tid;
+    const int4 e = i < lcnt && dec_ok(i < a.Npad, 7) ? (first ? r_first : llist[i]) : int4{-1, 0, 0, 0};
+    int r = e.x < 0 ? -1 : live_row(e);
+    if (r >= 0 && !dec_ok(r < a.Npad && live_time(e) < live_flen(e), 8)) r = -1;
+    T.rows[tid] = r;
+    T.walking[tid] = r >= 0;
+    T.emit_e[tid] = -1;
+    T.slot_[tid] = live_slot(e);
+    T.add_[tid] = live_added(e);
+    T.tidx[tid] = live_time(e);
+    T.flen_[tid] = live_flen(e);
+    T.idx_[tid] = live_idx(e);
+  }
+}
+// logits = ((s0 + s1) + s2) + s3 and the argmax over the 29 real labels: wave w takes rows 4w .. 4w+3,
+// 16 lanes per row with labels 2l, 2l+1, merged by cross-lane moves (larger value, ties to the smaller
+// label: torch.argmax's first maximum); the row's first lane applies greedy_decode_update
+// (decoder.py:137-167) to the tile state and the DecState arrays.  PS: the persistent launch stores
+// write-through, as a row's next step may run on another XCD whose L2 would otherwise write back
+// its own (newer) copy of the line first.
+template <bool PS>
+__device__ __forceinline__ void joint_argmax_update(JointTile& T, const DecArgs& a, int wave, int lane) {
+  const DecState& s = a.s;
+  const int m = 4 * wave + (lane >> 4), l2 = 2 * (lane & 15);
+  float bv = 0.0f;
+  int bl = -1;
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const int j = l2 + e;
+    const float v = ((T.Lp[0][m][j] + T.Lp[1][m][j]) + T.Lp[2][m][j]) + T.Lp[3][m][j];
+    if (j < NLAB && (bl < 0 || v > bv)) {
+      bv = v;
+      bl = j;
+    }
+  }
+#pragma unroll
+  for (int off = 1; off < 16; off <<= 1) {
+    const float ov = __shfl_xor(bv, off);
+    const int ol = __shfl_xor(bl, off);
+    if (ol >= 0 && (bl < 0 || ov > bv || (ov == bv && ol < bl))) {
+      bv = ov;
+      bl = ol;
+    }
+  }
+  if ((lane & 15) == 0 && T.walking[m]) {
+    const int row = T.rows[m], best = bl;
+    if (best != BLANK && T.add_[m] != MAXSYM) {
+      const int id = T.idx_[m] + 1;
+      T.idx_[m] = id;
+      st_b32<PS>(&s.idx[row], (uint32_t)id);
+      if (id < a.max_res) st_b32<PS>(&a.res[(size_t)row * a.max_res + id], (uint32_t)best);
+      st_b32<PS>(&s.added[row], (uint32_t)++T.add_[m]);
+      st_b32<PS>(&s.preg[row], (uint32_t)best);
+      const int nsl = T.slot_[m] ^ 1;  // commit the candidate (hg, cg) as (pre_hg, pre_cg)
+      T.slot_[m] = nsl;
+      st_b32<PS>(&s.slot[row], (uint32_t)nsl);
+      T.emit_e[m] = emit_entry(row, nsl, best);
+      T.walking[m] = 0;
+    } else {
+      const int fl = T.flen_[m];
+      int t = T.tidx[m] + 1;
+      if (t >= fl) {
+        st_b32<PS>(&s.fin[row], 1u);
+        T.walking[m] = 0;
+        T.rows[m] = -1;  // finished: not in the next live list
+        t = fl - 1;
+      }
+      T.tidx[m] = t;
+      st_b32<PS>(&s.time[row], (uint32_t)t);
+      st_b32<PS>(&s.added[row], 0u);
+      T.add_[m] = 0;
+    }
+  }
+}
+// Wave 0: the tile's emitting rows -> next emit list, its unfinished rows -> next live list.  ONE 64-bit
+// atomic on the adjacent (emit, live) counters of the next parity returns both bases.
+template <bool PS>
+__device__ __forceinline__ void joint_publish(const JointTile& T, const DecArgs& a, int parity, int lane) {
+  const DecState& s = a.s;
+  const int e = lane < JRT ? T.emit_e[lane] : -1;
+  const int r = lane < JRT ? T.rows[lane] : -1;
+  const unsigned long long me = __ballot(e >= 0), mr = __ballot(r >= 0);
+  unsigned long long base = 0;
+  if (lane == 0 && (me | mr)) {
+    const unsigned long long inc = (unsigned long long)__popcll(me) | ((unsigned long long)__popcll(mr) << 32);
+#ifndef RNNT_EMU
+    base = PS ? __hip_atomic_fetch_add((unsigned long long*)&s.count[EMIT_N(parity ^ 1)], inc, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT)
+              : atomicAdd((unsigned long long*)&s.count[EMIT_N(parity ^ 1)], inc);
+#else
+    base = atomicAdd((unsigned long long*)&s.count[EMIT_N(parity ^ 1)], inc);
+#endif
+  }
+  base = __shfl(base, 0);
+  const unsigned long long below = (1ull << lane) - 1;
+  if (lane == 0) dec_ok(false, 31);  // ran (the emulator's check that the joint executed)
+  if (e >= 0 && dec_ok((int)(base & 0xffffffffu) + __popcll(me & below) < a.Npad, 9))
+    st_b32<PS>(&s.list[(parity ^ 1) * a.Npad + (int)(base & 0xffffffffu) + __popcll(me & below)], (uint32_t)e);
+  if (r >= 0 && dec_ok((int)(base >> 32) + __popcll(mr & below) < a.Npad, 10)) {
+    const int4 le = live_entry(r, T.slot_[lane], T.add_[lane], T.tidx[lane], T.flen_[lane], T.idx_[lane]);
+    st_b128<PS>(&s.live[(parity ^ 1) * a.Npad + (int)(base >> 32) + __popcll(mr & below)],
+                uint4{(uint32_t)le.x, (uint32_t)le.y, (uint32_t)le.z, (uint32_t)le.w});
+  }
+}
+
 struct JointLds {
   __attribute__((aligned(16))) uint16_t X[JRT][YP];
-  float Lp[4][JRT][NLAB_PAD + 1];
-  int rows[JRT], walking[JRT], tidx[JRT], emit_e[JRT];
-  int slot_[JRT], add_[JRT], flen_[JRT], idx_[JRT];
+  JointTile T;
 };
 struct JointRegs {
   uint4 wv[8];  // W2 fragments: issued after the first tile's F / G loads (see dec_pred_kernel)
@@ -822,11 +945,11 @@ struct JointRegs {
 template <bool PS>
 __device__ __forceinline__ void dec_joint_body(const DecArgs& a, int parity, int jg, int njg, JointLds& L, JointRegs& W) {
   const DecState& s = a.s;
+  JointTile& T = L.T;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, c = lane & 15;
   ST_MARK(st0);
   const int4* llist = s.live + parity * a.Npad;
-  int4* nlist = s.live + (parity ^ 1) * a.Npad;
-  const int4 r_first = tid < JRT ? llist[jg * JRT + tid] : int4{0, 0, 0, 0};
+  const int4 r_first = tid < JRT ? llist[jg * JRT + tid] : int4{0, 0, 0, 0};  // beside the count: one round trip
   const int lcnt = s.count[LIVE_N(parity)];
   const int ntiles = (lcnt + JRT - 1) / JRT;
   if (jg >= ntiles) return;
@@ -834,20 +957,7 @@ __device__ __forceinline__ void dec_joint_body(const DecArgs& a, int parity, int
   // label half w&1 over k blocks 2(w>>1) and 2(w>>1)+1 as two independent 4-instruction chains
   const int lh = wave & 1, kb0 = 2 * (wave >> 1);
   for (int rt = jg; rt < ntiles; rt += njg) {
-    if (tid < JRT) {
-      const int i = rt * JRT + tid;
-      const int4 e = i < lcnt && dec_ok(i < a.Npad, 7) ? (rt == jg ? r_first : llist[i]) : int4{-1, 0, 0, 0};
-      int r = e.x < 0 ? -1 : entry_row(e.x);
-      if (r >= 0 && !dec_ok(r < a.Npad && (e.y & 0xffff) < ((e.y >> 16) & 0xffff), 8)) r = -1;
-      L.rows[tid] = r;
-      L.walking[tid] = r >= 0;
-      L.emit_e[tid] = -1;
-      L.slot_[tid] = (e.x >> 24) & 1;
-      L.add_[tid] = (e.x >> 25) & 31;
-      L.tidx[tid] = e.y & 0xffff;
-      L.flen_[tid] = (e.y >> 16) & 0xffff;
-      L.idx_[tid] = e.z;
-    }
+    joint_load_tile(T, a, llist, lcnt, rt, rt == jg, r_first, tid);
     lds_barrier();
     ST_MARK(st1);
 #ifdef RNNT_DEV_STAMPS
@@ -857,7 +967,7 @@ __device__ __forceinline__ void dec_joint_body(const DecArgs& a, int parity, int
     float4 gl4[NIT][2];
     for (int it = 0; it < JOINT_ITERS; ++it) {
       bool any = false;
-      for (int m = 0; m < JRT; ++m) any |= L.walking[m] != 0;
+      for (int m = 0; m < JRT; ++m) any |= T.walking[m] != 0;
       if (!any) break;
       // every load of the tile first (one memory round trip), then y1: rows not walking read a
       // safe cached address (row 0 of frame 0) and stage zeros.  G is the same for every frame
@@ -867,8 +977,8 @@ __device__ __forceinline__ void dec_joint_body(const DecArgs& a, int parity, int
 #pragma unroll
       for (int u = 0; u < NIT; ++u) {
         const int i = tid + 256 * u, m = i / (J / 8), k = (i % (J / 8)) * 8;
-        wk[u] = L.walking[m] != 0;
-        const int row = wk[u] ? L.rows[m] : 0, tm = wk[u] ? L.tidx[m] : 0;
+        wk[u] = T.walking[m] != 0;
+        const int row = wk[u] ? T.rows[m] : 0, tm = wk[u] ? T.tidx[m] : 0;
         const float* fr = a.F + ((size_t)tm * a.Npad + row) * J + k;
         fl4[u][0] = __builtin_nontemporal_load((const v4f*)fr);  // streamed once
         fl4[u][1] = __builtin_nontemporal_load((const v4f*)(fr + 4));
@@ -911,7 +1021,7 @@ __device__ __forceinline__ void dec_joint_body(const DecArgs& a, int parity, int
       }
       lds_barrier();
       ST_SET(st2);
-      if (__any(L.walking[c] != 0)) {
+      if (__any(T.walking[c] != 0)) {
         const uint16_t* xr = &L.X[c][8 * q];
         v4f s0 = W.bias, s1 = v4f{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -921,101 +1031,16 @@ __device__ __forceinline__ void dec_joint_body(const DecArgs& a, int parity, int
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          L.Lp[kb0][c][lh * 16 + 4 * q + r] = s0[r];
-          L.Lp[kb0 + 1][c][lh * 16 + 4 * q + r] = s1[r];
+          T.Lp[kb0][c][lh * 16 + 4 * q + r] = s0[r];
+          T.Lp[kb0 + 1][c][lh * 16 + 4 * q + r] = s1[r];
         }
       }
       lds_barrier();
-      // logits = ((s0 + s1) + s2) + s3 and the argmax over the 29 real labels: wave w takes rows
-      // 4w .. 4w+3, 16 lanes per row with labels 2l, 2l+1, merged by cross-lane moves (larger
-      // value, ties to the smaller label: torch.argmax's first maximum); the row's first lane
-      // applies greedy_decode_update
-      {
-        const int m = 4 * wave + (lane >> 4), l2 = 2 * (lane & 15);
-        float bv = 0.0f;
-        int bl = -1;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const int j = l2 + e;
-          const float v = ((L.Lp[0][m][j] + L.Lp[1][m][j]) + L.Lp[2][m][j]) + L.Lp[3][m][j];
-          if (j < NLAB && (bl < 0 || v > bv)) {
-            bv = v;
-            bl = j;
-          }
-        }
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1) {
-          const float ov = __shfl_xor(bv, off);
-          const int ol = __shfl_xor(bl, off);
-          if (ol >= 0 && (bl < 0 || ov > bv || (ov == bv && ol < bl))) {
-            bv = ov;
-            bl = ol;
-          }
-        }
-        if ((lane & 15) == 0) {
-          if (L.walking[m]) {
-            const int row = L.rows[m], best = bl;
-            if (best != BLANK && L.add_[m] != MAXSYM) {
-              const int id = L.idx_[m] + 1;
-              L.idx_[m] = id;
-              // persistent launch: write-through, as a row's next step may run on another XCD
-              // whose L2 would otherwise write back its own (newer) copy of the line first
-              st_b32<PS>(&s.idx[row], (uint32_t)id);
-              if (id < a.max_res) st_b32<PS>(&a.res[(size_t)row * a.max_res + id], (uint32_t)best);
-              st_b32<PS>(&s.added[row], (uint32_t)++L.add_[m]);
-              st_b32<PS>(&s.preg[row], (uint32_t)best);
-              const int nsl = L.slot_[m] ^ 1;  // commit the candidate (hg, cg) as (pre_hg, pre_cg)
-              L.slot_[m] = nsl;
-              st_b32<PS>(&s.slot[row], (uint32_t)nsl);
-              L.emit_e[m] = emit_entry(row, nsl, best);
-              L.walking[m] = 0;
-            } else {
-              const int fl = L.flen_[m];
-              int t = L.tidx[m] + 1;
-              if (t >= fl) {
-                st_b32<PS>(&s.fin[row], 1u);
-                L.walking[m] = 0;
-                L.rows[m] = -1;  // finished: not in the next live list
-                t = fl - 1;
-              }
-              L.tidx[m] = t;
-              st_b32<PS>(&s.time[row], (uint32_t)t);
-              st_b32<PS>(&s.added[row], 0u);
-              L.add_[m] = 0;
-            }
-          }
-        }
-      }
+      joint_argmax_update<PS>(T, a, wave, lane);
       lds_barrier();
     }
-    // the tile's emitting rows -> next emit list, its unfinished rows -> next live list: ONE
-    // 64-bit atomic on the adjacent (emit, live) counters of the next parity returns both bases
-    if (wave == 0) {
-      const int e = lane < JRT ? L.emit_e[lane] : -1;
-      const int r = lane < JRT ? L.rows[lane] : -1;
-      const unsigned long long me = __ballot(e >= 0), mr = __ballot(r >= 0);
-      unsigned long long base = 0;
-      if (lane == 0 && (me | mr)) {
-        const unsigned long long inc = (unsigned long long)__popcll(me) | ((unsigned long long)__popcll(mr) << 32);
-#ifndef RNNT_EMU
-        base = PS ? __hip_atomic_fetch_add((unsigned long long*)&s.count[EMIT_N(parity ^ 1)], inc, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT)
-                  : atomicAdd((unsigned long long*)&s.count[EMIT_N(parity ^ 1)], inc);
-#else
-        base = atomicAdd((unsigned long long*)&s.count[EMIT_N(parity ^ 1)], inc);
-#endif
-      }
-      base = __shfl(base, 0);
-      const unsigned long long below = (1ull << lane) - 1;
-      if (lane == 0) dec_ok(false, 31);  // ran (the emulator's check that the joint executed)
-      if (e >= 0 && dec_ok((int)(base & 0xffffffffu) + __popcll(me & below) < a.Npad, 9))
-        st_b32<PS>(&s.list[(parity ^ 1) * a.Npad + (int)(base & 0xffffffffu) + __popcll(me & below)], (uint32_t)e);
-      if (r >= 0 && dec_ok((int)(base >> 32) + __popcll(mr & below) < a.Npad, 10)) {
-        const int4 le = live_entry(r, L.slot_[lane], L.add_[lane], L.tidx[lane], L.flen_[lane], L.idx_[lane]);
-        st_b128<PS>(&nlist[(int)(base >> 32) + __popcll(mr & below)], uint4{(uint32_t)le.x, (uint32_t)le.y, (uint32_t)le.z, (uint32_t)le.w});
-      }
-    }
-    lds_barrier();  // rows / walking / tidx / X are reused by the next row tile
+    if (wave == 0) joint_publish<PS>(T, a, parity, lane);
+    lds_barrier();  // the tile state and X are reused by the next row tile
     ST_FLUSH(3, st0, st1, st2, 0ull);
   }
 }
@@ -1030,50 +1055,36 @@ __global__ void __launch_bounds__(256) dec_joint_kernel(DecArgs a, int parity) {
 // workgroup.  No y1 staging: wave w takes k block w (k = 128w .. 128w + 127) for both label halves and
 // builds its B fragments in registers straight from F and G (the 8 k of row c that the MFMA's lane
 // (q, c) takes: F and G for 16 rows x 128 k per wave, each element loaded once per tile); its two
-// chains are s_w of the step kernel (from b2 on block 0, from 0 on the others), so the logits
-// ((s0 + s1) + s2) + s3 and everything after them are the step kernel's.  G is re-read each walk
-// iteration (the step kernel keeps it in registers).
+// chains are s_w of dec_joint_body (from b2 on block 0, from 0 on the others) and land in the same
+// Lp, so the logits ((s0 + s1) + s2) + s3 and everything after them are the shared
+// joint_argmax_update / joint_publish.  G is re-read each walk iteration (dec_joint_body keeps it in
+// registers).
 struct JointSlimLds {
-  float Lp[4][JRT][NLAB_PAD + 1];
-  int rows[JRT], walking[JRT], tidx[JRT], emit_e[JRT];
-  int slot_[JRT], add_[JRT], flen_[JRT], idx_[JRT];
+  JointTile T;
 };
 __global__ void SLIM_BOUNDS dec_joint_slim_kernel(DecArgs a, int parity) {
   __shared__ JointSlimLds L;
+  JointTile& T = L.T;
   const DecState& s = a.s;
   const int jg = blockIdx.x, njg = gridDim.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, c = lane & 15;
   const int4* llist = s.live + parity * a.Npad;
-  int4* nlist = s.live + (parity ^ 1) * a.Npad;
-  const int4 r_first = tid < JRT ? llist[jg * JRT + tid] : int4{0, 0, 0, 0};
+  const int4 r_first = tid < JRT ? llist[jg * JRT + tid] : int4{0, 0, 0, 0};  // beside the count: one round trip
   const int lcnt = s.count[LIVE_N(parity)];
   const int ntiles = (lcnt + JRT - 1) / JRT;
   if (jg >= ntiles) return;
   for (int rt = jg; rt < ntiles; rt += njg) {
-    if (tid < JRT) {
-      const int i = rt * JRT + tid;
-      const int4 e = i < lcnt && dec_ok(i < a.Npad, 7) ? (rt == jg ? r_first : llist[i]) : int4{-1, 0, 0, 0};
-      int r = e.x < 0 ? -1 : entry_row(e.x);
-      if (r >= 0 && !dec_ok(r < a.Npad && (e.y & 0xffff) < ((e.y >> 16) & 0xffff), 8)) r = -1;
-      L.rows[tid] = r;
-      L.walking[tid] = r >= 0;
-      L.emit_e[tid] = -1;
-      L.slot_[tid] = (e.x >> 24) & 1;
-      L.add_[tid] = (e.x >> 25) & 31;
-      L.tidx[tid] = e.y & 0xffff;
-      L.flen_[tid] = (e.y >> 16) & 0xffff;
-      L.idx_[tid] = e.z;
-    }
+    joint_load_tile(T, a, llist, lcnt, rt, rt == jg, r_first, tid);
     lds_barrier();
 #pragma unroll 1
     for (int it = 0; it < JOINT_ITERS; ++it) {
       bool any = false;
-      for (int m = 0; m < JRT; ++m) any |= L.walking[m] != 0;
+      for (int m = 0; m < JRT; ++m) any |= T.walking[m] != 0;
       if (!any) break;
       // this lane's row: F at its walk frame and G (rows not walking read row 0 of frame 0: their
       // columns are computed and dropped)
-      const bool wk = L.walking[c] != 0;
-      const int row = wk ? L.rows[c] : 0, tm = wk ? L.tidx[c] : 0;
+      const bool wk = T.walking[c] != 0;
+      const int row = wk ? T.rows[c] : 0, tm = wk ? T.tidx[c] : 0;
       const float* fr = a.F + ((size_t)tm * a.Npad + row) * J + 128 * wave + 8 * q;
       const float* gr = a.G + (size_t)row * J + 128 * wave + 8 * q;
       // W2 fragments (label half h, k = 128 wave + 32 b + 8 q; re-read each iteration, L1 / L2
@@ -1129,86 +1140,15 @@ __global__ void SLIM_BOUNDS dec_joint_slim_kernel(DecArgs a, int parity) {
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        L.Lp[wave][c][4 * q + r] = s0[r];
-        L.Lp[wave][c][16 + 4 * q + r] = s1[r];
+        T.Lp[wave][c][4 * q + r] = s0[r];
+        T.Lp[wave][c][16 + 4 * q + r] = s1[r];
       }
       lds_barrier();
-      // the step kernel's argmax and greedy_decode_update (dec_joint_body)
-      {
-        const int m = 4 * wave + (lane >> 4), l2 = 2 * (lane & 15);
-        float bv = 0.0f;
-        int bl = -1;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const int j = l2 + e;
-          const float v = ((L.Lp[0][m][j] + L.Lp[1][m][j]) + L.Lp[2][m][j]) + L.Lp[3][m][j];
-          if (j < NLAB && (bl < 0 || v > bv)) {
-            bv = v;
-            bl = j;
-          }
-        }
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1) {
-          const float ov = __shfl_xor(bv, off);
-          const int ol = __shfl_xor(bl, off);
-          if (ol >= 0 && (bl < 0 || ov > bv || (ov == bv && ol < bl))) {
-            bv = ov;
-            bl = ol;
-          }
-        }
-        if ((lane & 15) == 0 && L.walking[m]) {
-          const int row = L.rows[m], best = bl;
-          if (best != BLANK && L.add_[m] != MAXSYM) {
-            const int id = L.idx_[m] + 1;
-            L.idx_[m] = id;
-            s.idx[row] = id;
-            if (id < a.max_res) a.res[(size_t)row * a.max_res + id] = best;
-            s.added[row] = ++L.add_[m];
-            s.preg[row] = best;
-            const int nsl = L.slot_[m] ^ 1;  // commit the candidate (hg, cg) as (pre_hg, pre_cg)
-            L.slot_[m] = nsl;
-            s.slot[row] = nsl;
-            L.emit_e[m] = emit_entry(row, nsl, best);
-            L.walking[m] = 0;
-          } else {
-            const int fl = L.flen_[m];
-            int t = L.tidx[m] + 1;
-            if (t >= fl) {
-              s.fin[row] = 1;
-              L.walking[m] = 0;
-              L.rows[m] = -1;  // finished: not in the next live list
-              t = fl - 1;
-            }
-            L.tidx[m] = t;
-            s.time[row] = t;
-            s.added[row] = 0;
-            L.add_[m] = 0;
-          }
-        }
-      }
+      joint_argmax_update<false>(T, a, wave, lane);
       lds_barrier();
     }
-    // the tile's emitting rows -> next emit list, its unfinished rows -> next live list (one 64-bit atomic)
-    if (wave == 0) {
-      const int e = lane < JRT ? L.emit_e[lane] : -1;
-      const int r = lane < JRT ? L.rows[lane] : -1;
-      const unsigned long long me = __ballot(e >= 0), mr = __ballot(r >= 0);
-      unsigned long long base = 0;
-      if (lane == 0 && (me | mr)) {
-        const unsigned long long inc = (unsigned long long)__popcll(me) | ((unsigned long long)__popcll(mr) << 32);
-        base = atomicAdd((unsigned long long*)&s.count[EMIT_N(parity ^ 1)], inc);
-      }
-      base = __shfl(base, 0);
-      const unsigned long long below = (1ull << lane) - 1;
-      if (lane == 0) dec_ok(false, 31);  // ran (the emulator's check that the joint executed)
-      if (e >= 0 && dec_ok((int)(base & 0xffffffffu) + __popcll(me & below) < a.Npad, 9))
-        s.list[(parity ^ 1) * a.Npad + (int)(base & 0xffffffffu) + __popcll(me & below)] = e;
-      if (r >= 0 && dec_ok((int)(base >> 32) + __popcll(mr & below) < a.Npad, 10)) {
-        const int4 le = live_entry(r, L.slot_[lane], L.add_[lane], L.tidx[lane], L.flen_[lane], L.idx_[lane]);
-        nlist[(int)(base >> 32) + __popcll(mr & below)] = le;
-      }
-    }
-    lds_barrier();  // rows / walking / tidx are reused by the next row tile
+    if (wave == 0) joint_publish<false>(T, a, parity, lane);
+    lds_barrier();  // the tile state is reused by the next row tile
   }
 }
 
@@ -1345,7 +1285,6 @@ int launch_greedy_decode(const DecArgs& a, int32_t* host_flags, hipEvent_t* evs,
   for (const void* p : need)
     if (!p) return -1;
   if (a.Npad % DEC_RT || a.N > a.Npad || a.Npad >= (1 << 24)) return -1;
-  const int rt = a.Npad / DEC_RT;
   if (hipMemsetAsync(a.s.count, 0, 4 * sizeof(int32_t), st) != hipSuccess) return -1;
   if (reset) {
     hipLaunchKernelGGL(dec_reset_res_kernel, dim3(a.N), dim3(256), 0, st, a.res, a.max_res, reset);
@@ -1402,12 +1341,19 @@ int launch_greedy_decode(const DecArgs& a, int32_t* host_flags, hipEvent_t* evs,
   int step = 0, chunk = 0;
   int live_bound = a.N;  // unfinished rows at the end of the last chunk read back (an upper bound)
   bool done = false;
+  // workgroups along the rows of a launch with `tile` rows per workgroup: the tiles the live rows need
+  // (never more than the batch has), at least 1, at most `cap`
+  const auto row_groups = [&](int tile, int cap) {
+    const int all = a.Npad / tile, need = (live_bound + tile - 1) / tile;
+    const int g = need < all ? need : all, g1 = g > 0 ? g : 1;
+    return g1 < cap ? g1 : cap;
+  };
   while (!done && step < a.max_iter) {
 #ifndef RNNT_EMU
     if (PERSIST_ROWS > 0 && chunk > 0 && live_bound <= PERSIST_ROWS) {
       // the chunks already enqueued run first (stream order); the persistent launch continues at
       // `step` with at most live_bound rows (live counts only fall)
-      const int nj = (live_bound + JRT - 1) / JRT > 0 ? (live_bound + JRT - 1) / JRT : 1;
+      const int nj = row_groups(JRT, a.Npad / JRT);  // one joint workgroup per live tile, uncapped
       if (set_smem_attr_once((const void*)dec_persist_kernel, (int)ps_lds_bytes(), ps_attr)) return -1;
       if (hipMemsetAsync(a.s.pc, 0, PC_WORDS * sizeof(uint32_t), st) != hipSuccess) return -1;
       hipLaunchKernelGGL(dec_persist_kernel, dim3(PS_P0 + PS_P1 + PS_G + nj), dim3(256), ps_lds_bytes(), st, a, a.s.pc,
@@ -1424,17 +1370,10 @@ int launch_greedy_decode(const DecArgs& a, int32_t* host_flags, hipEvent_t* evs,
 #endif
     const int csz = live_bound > TAIL_ROWS ? CHUNK : TAIL_CHUNK;
     // row-tile workgroups per launch: one resident round, and no more than the live rows need
-    const int lt = (live_bound + DEC_RT - 1) / DEC_RT < rt ? (live_bound + DEC_RT - 1) / DEC_RT : rt;
-    const int lt1 = lt > 0 ? lt : 1;
-    const int rg_pred = lt1 < RG[0] ? lt1 : RG[0];
-    const int rg_g = lt1 < RG[1] ? lt1 : RG[1];
-    const int ljt = (live_bound + JRT - 1) / JRT > 0 ? (live_bound + JRT - 1) / JRT : 1;
-    const int rg_joint = ljt < RG[2] ? ljt : RG[2];
+    const int rg_pred = row_groups(DEC_RT, RG[0]), rg_g = row_groups(DEC_RT, RG[1]), rg_joint = row_groups(JRT, RG[2]);
     // co-resident kernels: 16-row tiles, the same row-group caps (twice as many: 120.4-122.8k vs 122.4-
     // 123.6k utt/s on one box; 6-8 pred groups lose 9 % isolated, MEASUREMENTS section 9)
-    const int ls = (live_bound + SLIM_RT - 1) / SLIM_RT < a.Npad / SLIM_RT ? (live_bound + SLIM_RT - 1) / SLIM_RT : a.Npad / SLIM_RT;
-    const int ls1 = ls > 0 ? ls : 1;
-    const int sg_pred = ls1 < RG[0] ? ls1 : RG[0], sg_g = ls1 < RG[1] ? ls1 : RG[1];
+    const int sg_pred = row_groups(SLIM_RT, RG[0]), sg_g = row_groups(SLIM_RT, RG[1]);
     for (int i = 0; i < csz && step < a.max_iter; ++i, ++step) {
       const int p = step & 1;
       if (SLIM & 2)

@@ -36,3 +36,15 @@ def test_decode_kernels_match_oracle_on_the_emulator(emu, server, slim):
     assert r.returncode == 0, r.stdout + r.stderr
     assert "bounds checks: ok" in r.stdout, r.stdout
     assert "tokens identical" in r.stdout, r.stdout
+
+
+@pytest.mark.parametrize("slim", ["15", "0"])
+def test_decode_kernels_walk_several_tiles_on_the_emulator(emu, slim):
+    # 40 rows, 6 frames, one row group per kernel (RNNT_DEC_RG=1x1x1): a single workgroup walks three
+    # 16-row joint tiles and two (big-tile) or three (co-resident) emit-list tiles -- the tile loops of
+    # the list, staging and joint helpers, which the 6-row case above never enters
+    r = subprocess.run([emu, "40", "6", "5", "0", "12"], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, RNNT_DEC_SLIM=slim, RNNT_DEC_RG="1x1x1"))
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "bounds checks: ok" in r.stdout, r.stdout
+    assert "tokens identical" in r.stdout, r.stdout

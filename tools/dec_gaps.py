@@ -18,16 +18,16 @@ import json
 import os
 import sys
 
+from dec_kinds import step_kind
+
 TAIL = 200
-KINDS = (("dec_pred_kernel<0", "pred0"), ("dec_pred_kernel<1", "pred1"), ("dec_g_kernel", "g"),
-         ("dec_joint_kernel", "joint"), ("copyBuffer", "copy"), ("dec_init", "init"), ("dec_finish", "finish"))
 
 
 def kind(name):
-    for k, v in KINDS:
+    for k, v in (("copyBuffer", "copy"), ("dec_init", "init"), ("dec_finish", "finish")):
         if k in name:
             return v
-    return None
+    return step_kind(name)
 
 
 def load(d):

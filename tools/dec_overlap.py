@@ -13,6 +13,8 @@ import glob
 import json
 import sys
 
+from dec_kinds import step_kind
+
 
 def main():
     rows = []
@@ -36,20 +38,20 @@ def main():
         i = bisect.bisect_right(starts, t) - 1
         return i >= 0 and pmax[i] > t
 
-    kinds = {"dec_pred_kernel<0": "pred0", "dec_pred_kernel<1": "pred1", "dec_g_kernel": "g", "dec_joint_kernel": "joint"}
     last_end = {}
     stats = {}
     for s, e, n, q, g in rows:
-        k = next((v for key, v in kinds.items() if key in n), None)
+        k = step_kind(n)
         if k is None:
             if "joint_trans" in n or "dec_init" in n:
                 last_end[q] = e
             continue
         gap = s - last_end[q] if q in last_end else None
         last_end[q] = e
-        # grid size: the step kernels launch one row group (pred 20, G 8 workgroups; joint <= 16 rows
-        # per workgroup) once few rows are live
-        size = "tail" if (k in ("pred0", "pred1") and g <= 20) or (k == "g" and g <= 8) or (k == "joint" and g <= 4) else "bulk"
+        # grid size: the step kernels launch one row group (pred 20 -- 40 where layer 1's h chain rides
+        # in the layer-0 launch --, G 8 workgroups; joint <= 16 rows per workgroup) once few rows are live
+        one_group = {"pred0": 40 if "pred0h" in n else 20, "pred1": 20, "g": 8, "joint": 4}[k]
+        size = "tail" if g <= one_group else "bulk"
         reg = ("overlapped" if tick_active(s) else "alone") + "/" + size
         d = stats.setdefault(reg, {}).setdefault(k, {"dur": [], "gap": []})
         d["dur"].append((e - s) / 1e3)

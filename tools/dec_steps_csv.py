@@ -13,17 +13,13 @@ import csv
 import json
 import sys
 
-KINDS = {"dec_pred_kernel<0": "pred0", "dec_pred_kernel<1": "pred1", "dec_g_kernel": "g", "dec_joint_kernel": "joint"}
+from dec_kinds import step_kind
+
 BUCKETS = [(0, 25), (25, 50), (50, 100), (100, 200), (200, 300), (300, 400), (400, 600), (600, 1000)]
 
 
 def kind(name):
-    for k, v in KINDS.items():
-        if k in name:
-            return v
-    if "dec_init" in name:
-        return "init"
-    return None
+    return "init" if "dec_init" in name else step_kind(name)
 
 
 def main():

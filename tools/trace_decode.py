@@ -11,6 +11,8 @@ import glob
 import json
 import sys
 
+from dec_kinds import step_kind
+
 
 def main():
     d = sys.argv[1]
@@ -40,11 +42,10 @@ def main():
     dur = collections.defaultdict(lambda: [[], []])
     gaps = [[], []]
     last_end = {}
-    dec = {"dec_pred_kernel", "dec_g_kernel", "dec_joint_kernel"}
     for s, e, n, q in rows:
         ov = 1 if enc_busy(s) else 0
         dur[n][ov].append(e - s)
-        if n in dec:
+        if step_kind(n) is not None:
             if q in last_end and s - last_end[q] < 1_000_000:
                 gaps[ov].append(s - last_end[q])
             last_end[q] = e

@@ -1,13 +1,16 @@
 """Per-step decode timeline from a rocprofv3 --kernel-trace CSV (measurement tooling).
 
     python tools/trace_steps.py <dir with *_kernel_trace.csv>
-Splits the trace into greedy steps (one dec_pred_kernel<0> starts each) and prints, for step
+Splits the trace into greedy steps (a layer-0 prediction launch of either kernel family --
+dec_kinds "pred0" -- starts each) and prints, for step
 ranges, the mean duration of each decode kernel and the mean step span (first start to last
 end), so the early (throughput) and tail (latency) regimes can be told apart.
 """
 import csv
 import glob
 import sys
+
+from dec_kinds import step_kind
 
 
 def main():
@@ -20,11 +23,12 @@ def main():
     rows.sort()
     steps, cur = [], None
     for s, e, n in rows:
-        if n.startswith("dec_pred_kernel<0"):
+        k = step_kind(n)
+        if k == "pred0":  # either family's layer-0 launch
             cur = {"start": s, "k": {}}
             steps.append(cur)
-        if cur is not None and n.startswith(("dec_pred", "dec_g", "dec_joint")):
-            cur["k"][n] = (s, e)
+        if cur is not None and k is not None:
+            cur["k"][k] = (s, e)
             cur["end"] = e
     # split into decodes: a gap > 1 ms between steps starts a new decode
     decs, d = [], []
@@ -47,7 +51,7 @@ def main():
             for x in seg:
                 for k, (s, e) in x["k"].items():
                     ks.setdefault(k, []).append((e - s) / 1e3)
-            kd = " ".join(f"{k.split('_')[1]}{k[-3:] if 'pred' in k else ''}={sum(v) / len(v):.1f}" for k, v in sorted(ks.items()))
+            kd = " ".join(f"{k}={sum(v) / len(v):.1f}" for k, v in sorted(ks.items()))
             print(f"  steps {lo:4d}-{min(hi, n):4d}: step {span:6.1f} us | {kd}")
 
 
