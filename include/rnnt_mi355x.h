@@ -128,6 +128,36 @@ int rnnt_engine_encode(rnnt_engine* e, const float* feats, const int32_t* lens, 
 int rnnt_engine_encode_gather(rnnt_engine* e, const float* store, const int64_t* offsets, const int32_t* lens,
                               const int32_t* lens_host, int T, int n, int n_pad, float* f_out, void* stream);
 
+/* ---- int8 feature ingest: the encoder's first step is x_q = q8(x * in_s[0]) (q8 = round half to
+ * even, clamp to [-128, 127]); a caller that keeps or moves features as int8 -- one byte per feature
+ * instead of four over PCIe and in HBM -- quantises once with the calls below and encodes with the
+ * _q8 entries.  Results are bit-identical to the fp32 entries (everything after the quantiser is
+ * int8 -> int32).  No reference counterpart (the reference quantises inside lstm_amx_int8). */
+/* in_s[0] of the loaded encoder: the scale every int8 feature byte given to this engine must have
+ * been made with.  RNNT_EINVAL while encoder layer 0 is not loaded. */
+int rnnt_engine_input_scale(const rnnt_engine* e, float* out);
+/* out[i] = q8(x[i] * scale) for i < n on host memory (no GPU call; any n >= 0, any alignment; x and
+ * out must not overlap).  Bit-identical to the device quantiser for every finite input and +-inf;
+ * NaN gives -128, as on the device. */
+int rnnt_quantize_features_host(const float* x, int64_t n, float scale, int8_t* out);
+/* The same on device memory of `device` (x fp32 16-byte aligned, out int8 4-byte aligned): quantises
+ * a resident feature store once. */
+int rnnt_quantize_features(const float* x, int64_t n, float scale, int8_t* out, int device, void* stream);
+/* rnnt_engine_encode from int8 features: feats device int8 [T][n_pad][256], 16-byte aligned (else
+ * RNNT_EINVAL), the AssembleSamples layout already quantised with rnnt_engine_input_scale's scale,
+ * zero past lens and in channels 240..255 (frames past a row's length and channels 240..255 are
+ * read as zero whatever they hold).  The engine copies the batch into its own workspace: once the
+ * call's work on the stream is done it never reads feats again.  Everything else as
+ * rnnt_engine_encode. */
+int rnnt_engine_encode_q8(rnnt_engine* e, const int8_t* feats, const int32_t* lens, const int32_t* lens_host, int T,
+                          int n, int n_pad, float* f_out, void* stream);
+/* rnnt_engine_encode_gather from an int8 store: store device int8 [rows][240] (each sample's
+ * [T_i][240] frames back to back, one frame = 240 B = 15 x 16 B), 16-byte aligned (else
+ * RNNT_EINVAL), bytes made with rnnt_engine_input_scale's scale; offsets / lens / lens_host as
+ * rnnt_engine_encode_gather. */
+int rnnt_engine_encode_gather_q8(rnnt_engine* e, const int8_t* store, const int64_t* offsets, const int32_t* lens,
+                                 const int32_t* lens_host, int T, int n, int n_pad, float* f_out, void* stream);
+
 /* Greedy decode of the last encoded batch: res device int32 [n][max_res] (filled with -1 first),
  * res_len device int32 [n]. */
 int rnnt_engine_decode(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_res, void* stream);
@@ -164,6 +194,16 @@ int rnnt_engine_encode_stream_pl(rnnt_engine* e, const float* store, const int64
                                  void* stream);
 int rnnt_engine_decode_stream_pl(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_res, const int32_t* reset,
                                  void* stream);
+/* The two stream encodes from an int8 feature store: store device int8 [rows][240], 16-byte aligned
+ * (else RNNT_EINVAL), bytes made with rnnt_engine_input_scale's scale (int8 feature ingest, above);
+ * every other argument, the slot state and the pairing with rnnt_engine_decode_stream /
+ * rnnt_engine_decode_stream_pl as for the fp32 calls. */
+int rnnt_engine_encode_stream_q8(rnnt_engine* e, const int8_t* store, const int64_t* offsets, const int32_t* lens,
+                                 const int32_t* lens_host, const int32_t* reset, int T, int n, int n_pad,
+                                 void* stream);
+int rnnt_engine_encode_stream_pl_q8(rnnt_engine* e, const int8_t* store, const int64_t* offsets, const int32_t* lens,
+                                    const int32_t* lens_host, const int32_t* reset, int T, int n, int n_pad,
+                                    void* stream);
 
 /* encode + decode. */
 int rnnt_engine_infer(rnnt_engine* e, const float* feats, const int32_t* lens, const int32_t* lens_host, int T,

@@ -76,6 +76,33 @@ __global__ void __launch_bounds__(256) quantize_gather_kernel(const float* __res
   }
 }
 
+// the last n % 4 elements of rnnt_quantize_features (quantize_kernel covers whole float4s)
+__global__ void __launch_bounds__(64) quantize_tail_kernel(const float* __restrict__ x, int n, float s,
+                                                           int8_t* __restrict__ out) {
+  if ((int)threadIdx.x < n) out[threadIdx.x] = q8(x[threadIdx.x] * s);
+}
+
+// AssembleSamples from features that are int8 already (int8 feature ingest, rnnt_mi355x.h): pure data
+// movement into the engine's x0q image [T][n_pad][256].  16 lanes cover one (frame, row) pair's 256
+// output bytes as 16 x 16 B: lanes 0..14 load the 15 aligned 16-byte pieces of the pair's 240 stored
+// bytes, lane 15 writes the zero channels 240..255; a pair past its row's length or in a padding
+// row is all zeros.  A wave moves four pairs per iteration (its stores are 1 KiB contiguous).
+// offsets != nullptr: the ragged store [rows][240] (frame f at 16-byte piece 15 f);
+// offsets == nullptr: the caller's dense [T][n_pad][256] image (pair p at piece 16 p), masked alike.
+__global__ void __launch_bounds__(256) gather_q8_kernel(const uint4* __restrict__ src,
+                                                        const int64_t* __restrict__ offsets,
+                                                        const int32_t* __restrict__ lens, int n, int n_pad,
+                                                        int64_t pairs, uint4* __restrict__ out) {
+  const int piece = threadIdx.x & 15;
+  const int64_t step = ((int64_t)gridDim.x * blockDim.x) >> 4;
+  for (int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4; p < pairs; p += step) {
+    const int row = (int)(p % n_pad), t = (int)(p / n_pad);
+    uint4 v = uint4{0u, 0u, 0u, 0u};
+    if (row < n && piece < 15 && t < lens[row]) v = offsets ? src[(offsets[row] + t) * 15 + piece] : src[p * 16 + piece];
+    out[p * 16 + piece] = v;
+  }
+}
+
 // ---------------------------------------------------------------- LSTM step
 // Workgroup tile: BM packed gate rows (BM/4 units) x BN batch rows, K swept in 128-byte stages;
 // 8 waves as 4 (gate) x 2 (batch), each wave WMT x WNT MFMA 16x16x64 tiles (BM = 64 WMT,
@@ -678,7 +705,19 @@ int launch_quantize(const float* feat, int64_t n, float s, int8_t* out, hipStrea
   int grid = (int)((n4 + 255) / 256);
   if (grid > 8192) grid = 8192;
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(quantize_kernel, dim3(grid), dim3(256), 0, st, (const float4*)feat, n4, s, (uint32_t*)out);
+  if (n4) hipLaunchKernelGGL(quantize_kernel, dim3(grid), dim3(256), 0, st, (const float4*)feat, n4, s, (uint32_t*)out);
+  if (n & 3) hipLaunchKernelGGL(quantize_tail_kernel, dim3(1), dim3(64), 0, st, feat + 4 * n4, (int)(n & 3), s, out + 4 * n4);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_gather_q8(const int8_t* src, const int64_t* offsets, const int32_t* lens, int T, int n, int n_pad,
+                     int8_t* out, hipStream_t st) {
+  const int64_t pairs = (int64_t)T * n_pad;
+  int grid = (int)((pairs * 16 + 255) / 256);
+  if (grid > 16384) grid = 16384;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(gather_q8_kernel, dim3(grid), dim3(256), 0, st, (const uint4*)src, offsets, lens, n, n_pad, pairs,
+                     (uint4*)out);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -62,12 +62,18 @@ __host__ __device__ inline uint64_t enc_tile_mask(uint64_t m128, int BN) {
   return m;
 }
 
+// out[i] = q8(feat[i] * s), n elements (any n: a last n % 4 elements go through a tail launch)
 int launch_quantize(const float* feat, int64_t n, float s, int8_t* out, hipStream_t st);
 // AssembleSamples + the layer-0 input quantizer in one pass: row i of the batch is the QSL sample
 // stored at store[offsets[i] * 240 ...] (LoadSamplesToRam's [T_i][240] fp32 rows, ragged), frames
 // t < lens[i]; out int8 [T][n_pad][256], zero past the length, in channels 240..255 and rows >= n.
 int launch_quantize_gather(const float* store, const int64_t* offsets, const int32_t* lens, int T, int n, int n_pad,
                            float s, int8_t* out, hipStream_t st);
+// The same assembly from int8 features (no arithmetic): src is the ragged int8 store [rows][240]
+// (offsets != nullptr) or a dense int8 [T][n_pad][256] image (offsets == nullptr), 16-byte aligned;
+// out as above.
+int launch_gather_q8(const int8_t* src, const int64_t* offsets, const int32_t* lens, int T, int n, int n_pad,
+                     int8_t* out, hipStream_t st);
 // tick tile shape: chosen per tick by the cost model (ENC_TILE_AUTO) or pinned (tests, sweeps);
 // ENC_TILE_FLOW: a whole-call encode of a small batch runs as one persistent dataflow launch
 // (lstm_i8_flow_kernel) instead of one launch per tick (the tick path treats it as AUTO)

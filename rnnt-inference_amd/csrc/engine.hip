@@ -24,6 +24,7 @@
 #include <hip/hip_ext.h>
 #include "encoder_f32.hpp"
 #include "decoder_f32.hpp"
+#include "quantize_host.hpp"
 #include "rnnt_device.hpp"
 
 using namespace rnnt;
@@ -725,12 +726,23 @@ __global__ void __launch_bounds__(64) enc_reset_rows_kernel(EncStateRows st, con
 }
 
 // The input of encode: an assembled [T][n_pad][256] fp32 batch, or the QSL's ragged sample store
-// gathered in the quantize pass (store != nullptr).
+// gathered in the quantize pass (store != nullptr); or either of them as int8 already (int8 feature
+// ingest: feats_q8 / store_q8, moved into x0q without arithmetic).
 struct EncInput {
   const float* feats = nullptr;
   const float* store = nullptr;
+  const int8_t* feats_q8 = nullptr;
+  const int8_t* store_q8 = nullptr;
   const int64_t* offsets = nullptr;
 };
+
+// gather_q8_kernel moves 16-byte pieces; a frame is 240 B = 15 pieces, so an aligned store's frames are
+// aligned.  Refused on the host, before anything is enqueued or the engine's mode changes.
+static int check_q8_alignment(const EncInput& in) {
+  if (((uintptr_t)in.feats_q8 | (uintptr_t)in.store_q8) & 15)
+    return fail(RNNT_EINVAL, "int8 features must be 16-byte aligned");
+  return 0;
+}
 
 // ---- persistent dataflow encode (lstm_i8_flow_kernel, encoder.hpp): the wavefront schedule's
 // layer-steps as one launch's task list.  Used for small batches (n_pad <= 256) when the engine's
@@ -862,8 +874,10 @@ static int run_flow(rnnt_engine* e, int T, int n_pad, const int32_t* lens, float
 // stream chunk (rnnt_engine_encode_stream): rows keep their state unless flagged.
 static int encode_impl(rnnt_engine* e, const EncInput& in, const int32_t* lens, const int32_t* lens_host, int T, int n,
                        int n_pad, float* f_out, void* stream, const int32_t* reset = nullptr, bool pl = false) {
-  if (!e || !lens || !(in.feats || (in.store && in.offsets))) return fail(RNNT_EINVAL, "null argument");
+  if (!e || !lens || !(in.feats || in.feats_q8 || ((in.store || in.store_q8) && in.offsets)))
+    return fail(RNNT_EINVAL, "null argument");
   if (e->enc_loaded != 0x1f) return fail(RNNT_EINVAL, "encoder weights not loaded");
+  if (check_q8_alignment(in)) return RNNT_EINVAL;
   int r = check_batch(e, T, n, n_pad);
   if (r) return r;
   DEVICE_SCOPE(e->device);
@@ -888,8 +902,10 @@ static int encode_impl(rnnt_engine* e, const EncInput& in, const int32_t* lens, 
     HIPCHK(hipGetLastError());
   }
   hipEvent_t ev0 = e->prof ? new_event(st) : nullptr;
-  if (in.store ? launch_quantize_gather(in.store, in.offsets, lens, T, n, n_pad, e->in_s[0], e->x0q, st)
-               : launch_quantize(in.feats, (int64_t)T * n_pad * FEAT, e->in_s[0], e->x0q, st))
+  if (in.store_q8   ? launch_gather_q8(in.store_q8, in.offsets, lens, T, n, n_pad, e->x0q, st)
+      : in.feats_q8 ? launch_gather_q8(in.feats_q8, nullptr, lens, T, n, n_pad, e->x0q, st)
+      : in.store    ? launch_quantize_gather(in.store, in.offsets, lens, T, n, n_pad, e->in_s[0], e->x0q, st)
+                    : launch_quantize(in.feats, (int64_t)T * n_pad * FEAT, e->in_s[0], e->x0q, st))
     return fail(RNNT_EDEVICE, "quantize launch failed");
   // Wavefront schedule: tick tau runs layer 0 at frame tau, layer 1 at frame tau-1, and the
   // post_rnn layers 2/3/4 at stacked frame t' on ticks 2t'+3 / 2t'+4 / 2t'+5, i.e. as soon as
@@ -950,28 +966,88 @@ extern "C" int rnnt_engine_encode(rnnt_engine* e, const float* feats, const int3
   return encode_impl(e, in, lens, lens_host, T, n, n_pad, f_out, stream);
 }
 
-extern "C" int rnnt_engine_encode_gather(rnnt_engine* e, const float* store, const int64_t* offsets,
-                                         const int32_t* lens, const int32_t* lens_host, int T, int n, int n_pad,
-                                         float* f_out, void* stream) {
+// ---- int8 feature ingest (rnnt_mi355x.h): the layer-0 input quantiser as calls of its own
+extern "C" int rnnt_engine_input_scale(const rnnt_engine* e, float* out) {
+  if (!e || !out) return fail(RNNT_EINVAL, "null argument");
+  if (!(e->enc_loaded & 1)) return fail(RNNT_EINVAL, "encoder layer 0 not loaded");
+  *out = e->in_s[0];
+  return 0;
+}
+
+extern "C" int rnnt_quantize_features_host(const float* x, int64_t n, float scale, int8_t* out) {
+  if (n < 0 || (n > 0 && (!x || !out))) return fail(RNNT_EINVAL, "null argument or negative count");
+  quantize_features_host(x, n, scale, out);
+  return 0;
+}
+
+extern "C" int rnnt_quantize_features(const float* x, int64_t n, float scale, int8_t* out, int device, void* stream) {
+  if (n < 0 || (n > 0 && (!x || !out))) return fail(RNNT_EINVAL, "null argument or negative count");
+  if (((uintptr_t)x & 15) || ((uintptr_t)out & 3))
+    return fail(RNNT_EINVAL, "quantize_features: x must be 16-byte and out 4-byte aligned");
+  if (n == 0) return 0;
+  DEVICE_SCOPE(device);
+  if (launch_quantize(x, n, scale, out, (hipStream_t)stream)) return fail(RNNT_EDEVICE, "quantize launch failed");
+  return 0;
+}
+
+extern "C" int rnnt_engine_encode_q8(rnnt_engine* e, const int8_t* feats, const int32_t* lens,
+                                     const int32_t* lens_host, int T, int n, int n_pad, float* f_out, void* stream) {
+  EncInput in;
+  in.feats_q8 = feats;
+  return encode_impl(e, in, lens, lens_host, T, n, n_pad, f_out, stream);
+}
+
+// the fp32 and the int8 form of the three store-fed entries differ in `in` alone
+static int encode_gather_in(rnnt_engine* e, const EncInput& in, const int32_t* lens, const int32_t* lens_host, int T,
+                            int n, int n_pad, float* f_out, void* stream) {
   if (!lens_host) return fail(RNNT_EINVAL, "encode_gather needs the host lengths");
   for (int i = 0; i < n; ++i)
     if (lens_host[i] < 0 || lens_host[i] > T) return fail(RNNT_EINVAL, "a length exceeds T");
+  return encode_impl(e, in, lens, lens_host, T, n, n_pad, f_out, stream);
+}
+
+extern "C" int rnnt_engine_encode_gather(rnnt_engine* e, const float* store, const int64_t* offsets,
+                                         const int32_t* lens, const int32_t* lens_host, int T, int n, int n_pad,
+                                         float* f_out, void* stream) {
   EncInput in;
   in.store = store;
   in.offsets = offsets;
-  return encode_impl(e, in, lens, lens_host, T, n, n_pad, f_out, stream);
+  return encode_gather_in(e, in, lens, lens_host, T, n, n_pad, f_out, stream);
+}
+
+extern "C" int rnnt_engine_encode_gather_q8(rnnt_engine* e, const int8_t* store, const int64_t* offsets,
+                                            const int32_t* lens, const int32_t* lens_host, int T, int n, int n_pad,
+                                            float* f_out, void* stream) {
+  EncInput in;
+  in.store_q8 = store;
+  in.offsets = offsets;
+  return encode_gather_in(e, in, lens, lens_host, T, n, n_pad, f_out, stream);
+}
+
+static int encode_stream_in(rnnt_engine* e, const EncInput& in, const int32_t* lens, const int32_t* lens_host,
+                            const int32_t* reset, int T, int n, int n_pad, void* stream) {
+  if (!lens_host || !reset) return fail(RNNT_EINVAL, "encode_stream needs the host lengths and the reset flags");
+  for (int i = 0; i < n; ++i)
+    if (lens_host[i] < 0 || lens_host[i] > T) return fail(RNNT_EINVAL, "a chunk length exceeds T");
+  return encode_impl(e, in, lens, lens_host, T, n, n_pad, nullptr, stream, reset);
 }
 
 extern "C" int rnnt_engine_encode_stream(rnnt_engine* e, const float* store, const int64_t* offsets,
                                          const int32_t* lens, const int32_t* lens_host, const int32_t* reset, int T,
                                          int n, int n_pad, void* stream) {
-  if (!lens_host || !reset) return fail(RNNT_EINVAL, "encode_stream needs the host lengths and the reset flags");
-  for (int i = 0; i < n; ++i)
-    if (lens_host[i] < 0 || lens_host[i] > T) return fail(RNNT_EINVAL, "a chunk length exceeds T");
   EncInput in;
   in.store = store;
   in.offsets = offsets;
-  return encode_impl(e, in, lens, lens_host, T, n, n_pad, nullptr, stream, reset);
+  return encode_stream_in(e, in, lens, lens_host, reset, T, n, n_pad, stream);
+}
+
+extern "C" int rnnt_engine_encode_stream_q8(rnnt_engine* e, const int8_t* store, const int64_t* offsets,
+                                            const int32_t* lens, const int32_t* lens_host, const int32_t* reset,
+                                            int T, int n, int n_pad, void* stream) {
+  EncInput in;
+  in.store_q8 = store;
+  in.offsets = offsets;
+  return encode_stream_in(e, in, lens, lens_host, reset, T, n, n_pad, stream);
 }
 
 static int decode_impl(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_res, void* stream,
@@ -1056,21 +1132,18 @@ static int pl_init(rnnt_engine* e) {
   return r;
 }
 
-extern "C" int rnnt_engine_encode_stream_pl(rnnt_engine* e, const float* store, const int64_t* offsets,
-                                            const int32_t* lens, const int32_t* lens_host, const int32_t* reset,
-                                            int T, int n, int n_pad, void* stream) {
+static int encode_stream_pl_in(rnnt_engine* e, const EncInput& in, const int32_t* lens, const int32_t* lens_host,
+                               const int32_t* reset, int T, int n, int n_pad, void* stream) {
   if (!e || !lens_host || !reset) return fail(RNNT_EINVAL, "encode_stream_pl needs the host lengths and the reset flags");
   for (int i = 0; i < n; ++i)
     if (lens_host[i] < 0 || lens_host[i] > T) return fail(RNNT_EINVAL, "a chunk length exceeds T");
+  if (check_q8_alignment(in)) return RNNT_EINVAL;  // before the engine turns pipelined for good
   int r = 0;
   if (!e->pl_mode.load(std::memory_order_acquire)) {  // first pipelined call: after the earlier calls' work
     DEVICE_SCOPE(e->device);
     if ((r = pl_init(e)) || (r = state_acquire(e, pick(e, stream)))) return r;
     e->pl_mode.store(true, std::memory_order_release);
   }
-  EncInput in;
-  in.store = store;
-  in.offsets = offsets;
   if ((r = encode_impl(e, in, lens, lens_host, T, n, n_pad, nullptr, stream, reset, true))) return r;
   DEVICE_SCOPE(e->device);
   hipStream_t st = pick(e, stream);
@@ -1093,6 +1166,24 @@ extern "C" int rnnt_engine_encode_stream_pl(rnnt_engine* e, const float* store, 
     e->pl_enc_k = k + 1;
   }
   return 0;
+}
+
+extern "C" int rnnt_engine_encode_stream_pl(rnnt_engine* e, const float* store, const int64_t* offsets,
+                                            const int32_t* lens, const int32_t* lens_host, const int32_t* reset,
+                                            int T, int n, int n_pad, void* stream) {
+  EncInput in;
+  in.store = store;
+  in.offsets = offsets;
+  return encode_stream_pl_in(e, in, lens, lens_host, reset, T, n, n_pad, stream);
+}
+
+extern "C" int rnnt_engine_encode_stream_pl_q8(rnnt_engine* e, const int8_t* store, const int64_t* offsets,
+                                               const int32_t* lens, const int32_t* lens_host, const int32_t* reset,
+                                               int T, int n, int n_pad, void* stream) {
+  EncInput in;
+  in.store_q8 = store;
+  in.offsets = offsets;
+  return encode_stream_pl_in(e, in, lens, lens_host, reset, T, n, n_pad, stream);
 }
 
 // a pipelined decode that cannot run marks the engine failed (sticky) and wakes the encode side,

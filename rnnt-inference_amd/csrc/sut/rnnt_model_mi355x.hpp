@@ -79,6 +79,10 @@ struct Options {
   int engines_per_gpu = 4;   // Offline batches in flight per GPU (env RNNT_ENGINES_PER_GPU)
   int sockets = 2;           // `which` values the SUT passes (index & 1, torch_sut.cpp:145)
   bool encode_turns = true;  // encoders of one GPU take turns (env RNNT_ENCODE_TURNS=0 lets them overlap)
+  // the packing loop quantises each frame to int8 (rnnt_quantize_features_host with the engine's input
+  // scale) instead of copying its 960 bytes: staging and the copy to the device carry 240 B per frame and
+  // the encode reads the int8 store (env RNNT_HOST_Q8=1; same tokens; off by default)
+  bool host_q8 = false;
 };
 
 inline Options options_from_env() {
@@ -99,6 +103,7 @@ inline Options options_from_env() {
   if (o.gpus.empty()) throw std::runtime_error("TorchModel: no GPU");
   if (const char* k = std::getenv("RNNT_ENGINES_PER_GPU")) o.engines_per_gpu = std::max(1, std::atoi(k));
   if (const char* t = std::getenv("RNNT_ENCODE_TURNS")) o.encode_turns = std::atoi(t) != 0;
+  if (const char* q = std::getenv("RNNT_HOST_Q8")) o.host_q8 = std::atoi(q) != 0;
   return o;
 }
 
@@ -184,6 +189,7 @@ struct Chunk {
 struct CallStats {
   double pack = 0, copy = 0, turn_wait = 0, encode = 0, decode = 0;
   int64_t calls = 0, frames = 0, dense_calls = 0;  // dense: batches DMA'd from the SUT's pinned memory as they are
+  int64_t q8_calls = 0;                            // batches packed as int8 (Options::host_q8)
 };
 
 }  // namespace mi355x
@@ -448,7 +454,8 @@ class TorchModel {
   // Packs every row's frames of this call into the slot's pinned staging area (row i's frames back to
   // back from offsets[i], only the 240 real channels: AssembleSamples leaves channels 240..255 zero and
   // the engine's layer-0 weights there are zero), one copy to the device, then the encode -- after the
-  // GPU's earlier encoders (turns in arrival order).
+  // GPU's earlier encoders (turns in arrival order).  With Options::host_q8 the packing quantises: the
+  // staged store is int8, a quarter of the bytes.
   // split_len chunks that are consecutive slices of one contiguous batch (State::update's torch::split of f,
   // metadata.cpp:63) -> that batch as one chunk (a non-owning view; the chunks keep it alive for the call)
   static bool merge_adjacent(const std::vector<mi355x::Chunk>& chunks, std::vector<mi355x::Chunk>& out) {
@@ -509,7 +516,10 @@ class TorchModel {
     }
     const size_t o_off = 0, o_len = o_off + sizeof(int64_t) * n_pad, o_rst = o_len + sizeof(int32_t) * n_pad,
                  o_feat = (size_t)mi355x::round_up((int64_t)(o_rst + sizeof(int32_t) * n_pad), 256);
-    const size_t bytes = o_feat + (size_t)total * mi355x::kFeat * sizeof(float);
+    const bool q8 = opts_.host_q8;
+    float q8_scale = 0.0f;
+    if (q8) mi355x::check(rnnt_engine_input_scale(s.e, &q8_scale), "rnnt_engine_input_scale");
+    const size_t bytes = o_feat + (size_t)total * mi355x::kFeat * (q8 ? sizeof(int8_t) : sizeof(float));
     hcheck(hipSetDevice(s.device), "hipSetDevice");
     hcheck(hipStreamSynchronize(s.st), "sync");  // the staging area's previous copy has landed
     s.grow(bytes);
@@ -518,6 +528,7 @@ class TorchModel {
     int32_t* hr = (int32_t*)(s.host + o_rst);
     for (int i = 0; i < n_pad; ++i) hr[i] = reset && i < n ? (reset[i] ? 1 : 0) : 0;
     float* feat = (float*)(s.host + o_feat);
+    int8_t* feat_q8 = (int8_t*)(s.host + o_feat);
     const auto t0 = Clock::now();
     // blocks of 32 rows, frames outer: each frame's 32 source rows are one contiguous run of the
     // frame-major input, and the block writes 32 sequential destination streams (row-by-row packing
@@ -534,8 +545,13 @@ class TorchModel {
           for (int64_t i = i0; i < i1; ++i) tmax = std::max(tmax, lc[i]);
           for (int32_t t = 0; t < tmax; ++t) {
             const float* src = f[c].data_ptr<float>() + (int64_t)t * R * C;
-            for (int64_t i = i0; i < i1; ++i)
-              if (t < lc[i]) std::memcpy(feat + (base[i - i0] + t) * mi355x::kFeat, src + i * C, mi355x::kFeat * sizeof(float));
+            for (int64_t i = i0; i < i1; ++i) {
+              if (t >= lc[i]) continue;
+              if (q8)
+                (void)rnnt_quantize_features_host(src + i * C, mi355x::kFeat, q8_scale, feat_q8 + (base[i - i0] + t) * mi355x::kFeat);
+              else
+                std::memcpy(feat + (base[i - i0] + t) * mi355x::kFeat, src + i * C, mi355x::kFeat * sizeof(float));
+            }
           }
           for (int64_t i = i0; i < i1; ++i) base[i - i0] += lc[i];
         }
@@ -549,6 +565,7 @@ class TorchModel {
     const int32_t* d_len = (const int32_t*)(s.dev + o_len);
     s.d_reset = (int32_t*)(s.dev + o_rst);
     const float* store = (const float*)(s.dev + o_feat);
+    const int8_t* store_q8 = (const int8_t*)(s.dev + o_feat);  // o_feat is a multiple of 256: 16-byte aligned
     Gpu& g = *ls.gpu;
     uint64_t ticket = 0;
     if (opts_.encode_turns) {
@@ -560,9 +577,11 @@ class TorchModel {
     int rc = 0;
     hipError_t hr_sync = hipSuccess;
     if (reset)
-      rc = rnnt_engine_encode_stream(s.e, store, d_off, d_len, len.data(), s.d_reset, T, n, n_pad, s.st);
+      rc = q8 ? rnnt_engine_encode_stream_q8(s.e, store_q8, d_off, d_len, len.data(), s.d_reset, T, n, n_pad, s.st)
+              : rnnt_engine_encode_stream(s.e, store, d_off, d_len, len.data(), s.d_reset, T, n, n_pad, s.st);
     else
-      rc = rnnt_engine_encode_gather(s.e, store, d_off, d_len, len.data(), T, n, n_pad, nullptr, s.st);
+      rc = q8 ? rnnt_engine_encode_gather_q8(s.e, store_q8, d_off, d_len, len.data(), T, n, n_pad, nullptr, s.st)
+              : rnnt_engine_encode_gather(s.e, store, d_off, d_len, len.data(), T, n, n_pad, nullptr, s.st);
     if (rc == 0) hr_sync = hipStreamSynchronize(s.st);  // the encoder is free again: the next turn may go
     if (opts_.encode_turns) {
       std::lock_guard<std::mutex> l(g.turn_mu);
@@ -580,6 +599,7 @@ class TorchModel {
     stats_.encode += secs(t3, t4);
     stats_.calls++;
     stats_.frames += total;
+    stats_.q8_calls += q8 ? 1 : 0;
   }
 
   void run_encode_dense(const Lease& ls, const at::Tensor& x, const std::vector<int32_t>& len, int T, int n, int n_pad) {

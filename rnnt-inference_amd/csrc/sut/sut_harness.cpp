@@ -553,6 +553,7 @@ int main(int argc, char** argv) {
     std::cout << "], \"model_host_seconds\": {\"pack\": " << cs.pack << ", \"copy\": " << cs.copy
               << ", \"turn_wait\": " << cs.turn_wait << ", \"encode\": " << cs.encode << ", \"decode\": " << cs.decode
               << ", \"encode_calls\": " << cs.calls << ", \"dense_pinned_calls\": " << cs.dense_calls
+              << ", \"q8_calls\": " << cs.q8_calls
               << ", \"frames\": " << cs.frames << "}, \"pinned_assembly\": " << (qsl.pinned ? "true" : "false")
               << ", \"preassembled\": " << (a.num("preassemble", 0) != 0 ? "true" : "false")
               << ", \"sos_fill_checked\": " << (resp.check_fill ? "true" : "false") << "}"

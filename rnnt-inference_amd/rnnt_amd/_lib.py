@@ -86,6 +86,18 @@ _SIGS = {
                                                C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rnnt_engine_decode_stream_pl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                C.c_void_p]),
+    # int8 feature ingest: the fp32 entries' signatures with an int8 store / batch
+    "rnnt_engine_input_scale": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rnnt_quantize_features_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
+    "rnnt_quantize_features": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
+    "rnnt_engine_encode_q8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p]),
+    "rnnt_engine_encode_gather_q8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rnnt_engine_encode_stream_q8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "rnnt_engine_encode_stream_pl_q8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rnnt_op_lstm_bf16": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p]),
     "rnnt_op_joint_hidden": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p]),
     "rnnt_op_joint_logits": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),

@@ -32,6 +32,18 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _feature_entry(t, name):
+    """The C entry point for a feature tensor's dtype: fp32 -> ``name``, int8 (features quantised
+    with Engine.quantize / quantize_host) -> ``name``_q8.  Anything else is refused: the entries
+    take untyped pointers and would read the bytes as floats."""
+    import torch
+    if t.dtype == torch.float32:
+        return name
+    if t.dtype == torch.int8:
+        return name + "_q8"
+    raise TypeError(f"features must be torch.float32 or torch.int8 (pre-quantised), got {t.dtype}")
+
+
 class Engine:
     def __init__(self, pm: PreparedModel, device=0, max_batch=1024, max_frames=R.MAX_FEA_LEN, max_res=None,
                  _path=None):
@@ -91,37 +103,42 @@ class Engine:
 
     # ---------------------------------------------------------------- batch API
     def encode(self, feats, lens, lens_host=None, n=None, f_out=None, stream=None):
-        """feats: cuda fp32 [T, n_pad, 256]; lens: cuda int32 [n_pad]; lens_host: numpy [n]."""
+        """feats: cuda fp32 [T, n_pad, 256], or int8 (the same batch through ``quantize``); lens:
+        cuda int32 [n_pad]; lens_host: numpy [n]."""
+        entry = _feature_entry(feats, "rnnt_engine_encode")
         T, n_pad, ch = feats.shape
         assert ch == R.PADDED_INPUT_SIZE and feats.is_contiguous() and lens.is_contiguous()
         n = n if n is not None else (len(lens_host) if lens_host is not None else n_pad)
         lh = None
         if lens_host is not None:
             lh = np.ascontiguousarray(lens_host, np.int32)
-        rc = self._lib.rnnt_engine_encode(self._h, _ptr(feats), _ptr(lens), lh.ctypes.data if lh is not None else None,
-                                          T, n, n_pad, _ptr(f_out), _stream_handle(stream))
-        _lib.check(rc, "rnnt_engine_encode")
+        rc = getattr(self._lib, entry)(self._h, _ptr(feats), _ptr(lens), lh.ctypes.data if lh is not None else None,
+                                       T, n, n_pad, _ptr(f_out), _stream_handle(stream))
+        _lib.check(rc, entry)
 
     def encode_gather(self, store, offsets, lens, lens_host, T, n, n_pad, f_out=None, stream=None):
         """encode with AssembleSamples fused into the quantizer: store cuda fp32 [rows, 240] (the
-        QSL's ragged samples), offsets cuda int64 [n], lens cuda int32 [n_pad], lens_host [n]."""
+        QSL's ragged samples) or int8 (that store through ``quantize``), offsets cuda int64 [n], lens
+        cuda int32 [n_pad], lens_host [n]."""
+        entry = _feature_entry(store, "rnnt_engine_encode_gather")
         assert store.is_contiguous() and store.shape[1] == R.trans_input_size and offsets.dtype.itemsize == 8
         lh = np.ascontiguousarray(lens_host, np.int32)
-        rc = self._lib.rnnt_engine_encode_gather(self._h, _ptr(store), _ptr(offsets), _ptr(lens), lh.ctypes.data, T, n,
-                                                 n_pad, _ptr(f_out), _stream_handle(stream))
-        _lib.check(rc, "rnnt_engine_encode_gather")
+        rc = getattr(self._lib, entry)(self._h, _ptr(store), _ptr(offsets), _ptr(lens), lh.ctypes.data, T, n, n_pad,
+                                       _ptr(f_out), _stream_handle(stream))
+        _lib.check(rc, entry)
 
     def encode_stream(self, store, offsets, lens, lens_host, reset, T, n, n_pad, stream=None):
         """One chunk of Server continuous batching (PipelineState, metadata.cpp:97-194): slot i's
         chunk is lens_host[i] frames from store row offsets[i]; reset cuda int32 [n_pad] flags the
         slots that start a new utterance (their LSTM state restarts at zero), the others carry
-        their state from the previous chunk."""
+        their state from the previous chunk.  store fp32 or int8, as for encode_gather."""
+        entry = _feature_entry(store, "rnnt_engine_encode_stream")
         assert store.is_contiguous() and store.shape[1] == R.trans_input_size and offsets.dtype.itemsize == 8
         assert reset.dtype.itemsize == 4 and reset.numel() >= n_pad
         lh = np.ascontiguousarray(lens_host, np.int32)
-        rc = self._lib.rnnt_engine_encode_stream(self._h, _ptr(store), _ptr(offsets), _ptr(lens), lh.ctypes.data,
-                                                 _ptr(reset), T, n, n_pad, _stream_handle(stream))
-        _lib.check(rc, "rnnt_engine_encode_stream")
+        rc = getattr(self._lib, entry)(self._h, _ptr(store), _ptr(offsets), _ptr(lens), lh.ctypes.data, _ptr(reset),
+                                       T, n, n_pad, _stream_handle(stream))
+        _lib.check(rc, entry)
 
     def decode_stream(self, res, res_len, reset, stream=None):
         """Greedy decode of the last stream chunk, carrying each slot's prediction state and result
@@ -133,14 +150,15 @@ class Engine:
     def encode_stream_pl(self, store, offsets, lens, lens_host, reset, T, n, n_pad, stream=None):
         """Pipelined encode_stream (rnnt_engine_encode_stream_pl): chunk k+1's encode runs while
         chunk k decodes (decode_stream_pl from another thread).  Returns after chunk k-1's decode
-        has taken its inputs; reset must stay unchanged until this chunk's decode completed."""
+        has taken its inputs; reset must stay unchanged until this chunk's decode completed.
+        store fp32 or int8, as for encode_gather."""
+        entry = _feature_entry(store, "rnnt_engine_encode_stream_pl")
         assert store.is_contiguous() and store.shape[1] == R.trans_input_size and offsets.dtype.itemsize == 8
         assert reset.dtype.itemsize == 4 and reset.numel() >= n_pad
         lh = np.ascontiguousarray(lens_host, np.int32)
-        rc = self._lib.rnnt_engine_encode_stream_pl(self._h, _ptr(store), _ptr(offsets), _ptr(lens),
-                                                    lh.ctypes.data, _ptr(reset), T, n, n_pad,
-                                                    _stream_handle(stream))
-        _lib.check(rc, "rnnt_engine_encode_stream_pl")
+        rc = getattr(self._lib, entry)(self._h, _ptr(store), _ptr(offsets), _ptr(lens), lh.ctypes.data, _ptr(reset),
+                                       T, n, n_pad, _stream_handle(stream))
+        _lib.check(rc, entry)
 
     def decode_stream_pl(self, res, res_len, reset, stream=None):
         """Pipelined decode_stream: decodes the oldest chunk whose encode_stream_pl returned."""
@@ -160,6 +178,35 @@ class Engine:
         rc = self._lib.rnnt_engine_infer(self._h, _ptr(feats), _ptr(lens), lh.ctypes.data, T, n, n_pad,
                                          _ptr(res), _ptr(res_len), res.shape[1], _stream_handle(stream))
         _lib.check(rc, "rnnt_engine_infer")
+
+    # ---------------------------------------------------------------- int8 feature ingest
+    def input_scale(self):
+        """in_s[0] of the loaded encoder: the scale of the layer-0 input quantiser."""
+        s = C.c_float()
+        _lib.check(self._lib.rnnt_engine_input_scale(self._h, C.byref(s)), "rnnt_engine_input_scale")
+        return float(s.value)
+
+    def quantize_host(self, x):
+        """q8(x * input_scale()) of a host fp32 array -> int8 array of the same shape (no GPU call):
+        the bytes the encode calls take in place of fp32 features."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.empty(x.shape, np.int8)
+        rc = self._lib.rnnt_quantize_features_host(x.ctypes.data, x.size, self.input_scale(), out.ctypes.data)
+        _lib.check(rc, "rnnt_quantize_features_host")
+        return out
+
+    def quantize(self, x, stream=None):
+        """The same on the device: x cuda fp32 (contiguous) -> cuda int8 of the same shape; turns a
+        resident feature store into its int8 form once."""
+        import torch
+        if x.dtype != torch.float32:
+            raise TypeError(f"quantize takes torch.float32 features, got {x.dtype}")
+        assert x.is_contiguous()
+        out = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+        rc = self._lib.rnnt_quantize_features(_ptr(x), x.numel(), self.input_scale(), _ptr(out),
+                                              x.device.index or 0, _stream_handle(stream))
+        _lib.check(rc, "rnnt_quantize_features")
+        return out
 
     # ---------------------------------------------------------------- fp32 transcription
     def load_f32_encoder(self, layers):

@@ -20,6 +20,9 @@ build() {
   done
   g++ -std=c++17 -O2 -fPIC -c crash_report.cpp -o $OUTD/crash_report_$name.o &
   objs="$objs $OUTD/crash_report_$name.o"
+  # the host feature quantiser engine.hip calls, with the Makefile's flags for it
+  g++ -std=c++17 -O3 -fPIC -ffp-contract=off -fno-math-errno -c quantize_host.cpp -o $OUTD/quantize_host_$name.o &
+  objs="$objs $OUTD/quantize_host_$name.o"
   wait
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs -o $OUTD/lib_$name.so
   echo "built $OUTD/lib_$name.so"

@@ -42,6 +42,8 @@ def main():
                     help="1: every batch assembled before the timed region (the model's own rate, host assembly excluded)")
     ap.add_argument("--wav", action="store_true",
                     help="WAV=true: bench.py --wav's audio QSL in host memory, featurized by the AudioProcessor drop-in")
+    ap.add_argument("--host-q8", action="store_true",
+                    help="RNNT_HOST_Q8=1: the model packs each batch as int8 (a quarter of the staged and copied bytes)")
     ap.add_argument("--compare", default=None)
     ap.add_argument("--workdir", default=None)
     args = ap.parse_args()
@@ -82,7 +84,8 @@ def main():
            "--batch", str(args.batch), "--split-len", str(args.split_len), "--intra", str(args.intra),
            "--warmup", str(args.warmup), "--pinned", str(args.pinned), "--preassemble", str(args.preassemble),
            "--check-fill", str(args.check_fill), "--out", out]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)  # progress lines pass through on stderr
+    env = dict(os.environ, RNNT_HOST_Q8="1") if args.host_q8 else None
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, env=env)  # progress lines pass through on stderr
     if r.returncode != 0:
         sys.exit(r.returncode)
     res = json.loads(r.stdout.strip().splitlines()[-1])
@@ -91,6 +94,7 @@ def main():
                                     else "bench.py's GpuQSL (seed 4) in host memory"),
                        "rate": "host- and PCIe-inclusive: AssembleSamples on the host, the model's staged copy to HBM"}
     res["intra"] = args.intra
+    res["host_q8"] = bool(args.host_q8)
     if args.compare:
         d = np.load(args.compare)
         want, off = {}, 0
