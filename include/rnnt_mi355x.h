@@ -406,6 +406,28 @@ int rnnt_featurizer_run(rnnt_featurizer* f, const float* wav, const int64_t* off
 int rnnt_featurizer_run_rows(rnnt_featurizer* f, const float* wav, const int64_t* offsets, int64_t stride,
                              const int32_t* wav_lens, const int32_t* wav_lens_host, int n, float* feats,
                              const int64_t* row_off, int32_t* feat_lens, int max_frames, void* stream);
+/* The two entries above with int8 output, for the engine's int8 feature ingest (above): the audio
+ * path as a producer of int8 batches and stores, quantised in the featurizer's last kernel instead
+ * of by a second pass over fp32 features.  feats device int8, 16-byte aligned (else RNNT_EINVAL;
+ * the engine's q8 entries require that alignment): [T_out][n_pad][256] for rnnt_featurizer_run_q8
+ * (the input of rnnt_engine_encode_q8), rows of 240 bytes for rnnt_featurizer_run_rows_q8 (frame t
+ * of row n at feats + (row_off[n] + t) * 240, nothing else touched: a store for
+ * rnnt_engine_encode_gather_q8 / _encode_stream_q8 / _encode_stream_pl_q8).  scale is
+ * rnnt_engine_input_scale of the engine that will encode the bytes; finite and > 0 (else
+ * RNNT_EINVAL).  Every byte equals q8(v * scale), v being the fp32 value rnnt_featurizer_run /
+ * _run_rows writes at that position for the same arguments -- bit-identical to
+ * rnnt_quantize_features applied to that output -- and every padding position (frames past
+ * feat_lens[n], channels 240..255, rows n..n_pad-1) is a zero byte.  feat_lens and every other
+ * argument and check as for the fp32 entries.  The fp32 values pass through a scratch the
+ * featurizer object owns (rows x the call's longest row x 960 B, grow-only: no allocation per call
+ * once warmed; one featurizer object serves one stream at a time, as before).  No reference
+ * counterpart. */
+int rnnt_featurizer_run_q8(rnnt_featurizer* f, const float* wav, const int64_t* offsets, int64_t stride,
+                           const int32_t* wav_lens, const int32_t* wav_lens_host, int n, int n_pad, float scale,
+                           int8_t* feats, int32_t* feat_lens, int T_out, void* stream);
+int rnnt_featurizer_run_rows_q8(rnnt_featurizer* f, const float* wav, const int64_t* offsets, int64_t stride,
+                                const int32_t* wav_lens, const int32_t* wav_lens_host, int n, float scale,
+                                int8_t* feats, const int64_t* row_off, int32_t* feat_lens, int max_frames, void* stream);
 
 #ifdef __cplusplus
 }

@@ -21,10 +21,19 @@
 //   fz_norm_kernel    one workgroup per utterance: per-channel mean / unbiased variance over the
 //                     valid rows (fp64 sums, sequential: deterministic), normalise in place,
 //                     zero-fill the time / channel / batch padding (i_layernorm_pad, :239-250).
+//
+// int8 output (rnnt_featurizer_run_q8 / _run_rows_q8, for the engine's int8 feature ingest): the
+// same plan and logmel kernels write the log-mel values into an fp32 scratch the featurizer object
+// owns (row n's frame t at scratch + (n * T_s + t) * 240, T_s = the call's longest row; grow-only
+// like the plan: worst case 512 rows x 500 frames x 960 B ~ 246 MB per featurizer object), and
+//   fz_norm_q8_kernel one workgroup per output row: fz_norm_kernel's statistics from the scratch
+//                     (same sums, bit-identical mean / rstd), then q8((x - mean) * rstd * scale)
+//                     written as packed 32-bit words (4 channels per lane), padding as zero bytes.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -106,8 +115,10 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 __device__ __forceinline__ int stft_frames(int L) { return L > 0 ? 1 + L / FZ_HOP : 0; }  // features.py:212
 
-// feature frame t of row n: a [T_out][n_pad][256] batch, or ragged rows of 240 channels
+// feature frame t of row n: a [T_out][n_pad][256] batch, or ragged rows of 240 channels; in an
+// int8 run, the row's frame in the fp32 scratch
 __device__ __forceinline__ float* feat_row(const FzArgs& a, int n, int t) {
+  if (a.scr_T) return a.feats + ((size_t)n * (size_t)a.scr_T + t) * FZ_FEAT;
   return a.row_off ? a.feats + (size_t)(a.row_off[n] + t) * FZ_FEAT
                    : a.feats + ((size_t)t * a.n_pad + n) * FZ_FEAT_PAD;
 }
@@ -332,6 +343,99 @@ __global__ __launch_bounds__(NT) void fz_norm_kernel(FzArgs a) {
   for (; t < T_end; ++t) col[t * rs] = (live && t < Tn) ? (col[t * rs] - mean) * rstd : 0.0f;
 }
 
+// four channels of one frame as one word of int8: fz_norm_kernel's value (x - mean) * rstd, then
+// the engine's input quantiser on it exactly as quantize_kernel (encoder.hip) applies it
+__device__ __forceinline__ uint32_t norm_q8x4(const float4 x, const float* mean, const float* rstd, float s) {
+  const float v0 = (x.x - mean[0]) * rstd[0], v1 = (x.y - mean[1]) * rstd[1], v2 = (x.z - mean[2]) * rstd[2],
+              v3 = (x.w - mean[3]) * rstd[3];
+  const uint32_t b0 = (uint8_t)q8(v0 * s), b1 = (uint8_t)q8(v1 * s), b2 = (uint8_t)q8(v2 * s),
+                 b3 = (uint8_t)q8(v3 * s);
+  return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+}
+
+// fz_norm_kernel for an int8 run: the log-mel values are in the fp32 scratch (feat_row), the
+// output is int8.  Pass 1, thread c = channel: fz_norm_kernel's sums over the row's scratch
+// frames (the same additions in the same order: mean and rstd are bit-identical), left in LDS.
+// Pass 2, a lane = 4 adjacent channels = one 32-bit store.  Padded output: a wave writes one
+// (frame, row) pair's 256 bytes as 64 words (channels 240..255, frames >= Tn and rows >= n as
+// zero words), the workgroup 4 frames per step.  Ragged output (grid n): the row's Tn x 240 bytes
+// are one contiguous run of Tn x 60 words, as are its scratch frames; nothing else is written.
+__global__ __launch_bounds__(NT) void fz_norm_q8_kernel(FzArgs a) {
+  const int n = blockIdx.x, c = threadIdx.x;
+  const bool ragged = a.row_off != nullptr;
+  int Tn = 0;
+  if (n < a.n) Tn = (stft_frames(a.wav_lens[n]) + FZ_SPLICE - 1) / FZ_SPLICE;
+  Tn = min(Tn, a.T_out);
+  if (c == 0) a.feat_lens[n] = Tn;
+  __shared__ float s_mean[FZ_FEAT_PAD];
+  __shared__ float s_rstd[FZ_FEAT_PAD];
+  const float* src = feat_row(a, n, 0);  // read for Tn > 0 only (rows >= n have no scratch frames)
+  float mean = 0.0f, rstd = 0.0f;
+  if (c < FZ_FEAT && Tn > 0) {
+    const float* col = src + c;
+    const size_t rs = FZ_FEAT;
+    double s = 0.0, s2 = 0.0;
+    int t = 0;
+    for (; t + 4 <= Tn; t += 4) {
+      float x[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) x[u] = col[(t + u) * rs];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        s += (double)x[u];
+        s2 += (double)x[u] * (double)x[u];
+      }
+    }
+    for (; t < Tn; ++t) {
+      const double x = (double)col[t * rs];
+      s += x;
+      s2 += x * x;
+    }
+    const double m = s / Tn;
+    const double var = Tn > 1 ? fmax(s2 - s * m, 0.0) / (double)(Tn - 1) : 0.0;  // unbiased=1
+    mean = (float)m;
+    rstd = 1.0f / sqrtf((float)var + a.k.eps);
+  }
+  s_mean[c] = mean;
+  s_rstd[c] = rstd;
+  __syncthreads();
+  const float4* src4 = reinterpret_cast<const float4*>(src);  // 960-byte frames of a 16-byte aligned scratch
+  constexpr int FW = FZ_FEAT / 4;                             // 60 words of real channels per frame
+  if (ragged) {
+    uint32_t* dst = reinterpret_cast<uint32_t*>(a.feats_q8 + a.row_off[n] * FZ_FEAT);
+    const int words = Tn * FW;
+    for (int i = c; i < words; i += NT) {
+      const int c4 = i % FW;
+      dst[i] = norm_q8x4(src4[i], s_mean + 4 * c4, s_rstd + 4 * c4, a.q8_scale);
+    }
+    return;
+  }
+  const int wave = c >> 6, lane = c & 63;
+  const bool live = lane < FW;
+  float mv[4], rv[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    mv[u] = s_mean[4 * lane + u];
+    rv[u] = s_rstd[4 * lane + u];
+  }
+  constexpr int FPW = NT / 64;  // frames per workgroup step
+  const size_t ts = (size_t)a.n_pad * (FZ_FEAT_PAD / 4);  // words between a row's frames
+  uint32_t* dst = reinterpret_cast<uint32_t*>(a.feats_q8) + (size_t)n * (FZ_FEAT_PAD / 4) + lane;
+  for (int t0 = wave; t0 < a.T_out; t0 += 4 * FPW) {
+    float4 x[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int t = t0 + FPW * u;
+      x[u] = (live && t < Tn) ? src4[(size_t)t * FW + lane] : float4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int t = t0 + FPW * u;
+      if (t < a.T_out) dst[t * ts] = (live && t < Tn) ? norm_q8x4(x[u], mv, rv, a.q8_scale) : 0u;
+    }
+  }
+}
+
 }  // namespace
 
 }  // namespace rnnt
@@ -346,6 +450,8 @@ struct rnnt_featurizer {
   std::vector<void*> allocs;
   int2* plan = nullptr;
   size_t plan_cap = 0;  // chunks
+  float* scratch = nullptr;  // int8 runs: the log-mel values between fz_logmel and fz_norm_q8 (grow-only)
+  size_t scratch_cap = 0;    // floats
   size_t own_cu_lds = 0;  // RNNT_FZ_OWN_CU=1: dynamic LDS that leaves no room for another workgroup on the CU
 };
 
@@ -460,6 +566,7 @@ extern "C" void rnnt_featurizer_destroy(rnnt_featurizer* f) {
   DeviceScope dscope(f->device);
   for (void* p : f->allocs) (void)hipFree(p);
   if (f->plan) (void)hipFree(f->plan);
+  if (f->scratch) (void)hipFree(f->scratch);
   delete f;
 }
 
@@ -492,10 +599,12 @@ static int launch_logmel(const FzArgs& a, size_t chunks, size_t dyn_lds, hipStre
 
 extern "C" size_t rnnt_featurizer_own_cu_lds(const rnnt_featurizer* f) { return f ? f->own_cu_lds : 0; }
 
-// row_off == nullptr: padded [T_out][n_pad][256] output; else ragged rows (n_pad == n)
+// row_off == nullptr: padded [T_out][n_pad][256] output; else ragged rows (n_pad == n).  feats_q8 != nullptr:
+// an int8 run (feats unused: the fp32 values go through the featurizer's scratch)
 static int featurizer_run(rnnt_featurizer* f, const float* wav, const int64_t* offsets, int64_t stride,
                           const int32_t* wav_lens, const int32_t* wav_lens_host, int n, int n_pad, float* feats,
-                          const int64_t* row_off, int32_t* feat_lens, int T_out, void* stream) {
+                          int8_t* feats_q8, float scale, const int64_t* row_off, int32_t* feat_lens, int T_out,
+                          void* stream) {
   if (!offsets && stride <= 0 && n > 0) return fz_fail(RNNT_EINVAL, "need offsets or a positive stride");
   int64_t tmax = 0;
   for (int i = 0; i < n; ++i) {
@@ -517,6 +626,20 @@ static int featurizer_run(rnnt_featurizer* f, const float* wav, const int64_t* o
     f->plan_cap = chunks;
   }
   FzArgs a{};
+  if (feats_q8) {
+    a.scr_T = std::max<int64_t>(tmax, 1);
+    const size_t need = (size_t)n * (size_t)a.scr_T * FZ_FEAT;
+    if (need > f->scratch_cap) {
+      if (f->scratch) FZCHK(hipFree(f->scratch));
+      f->scratch = nullptr;
+      f->scratch_cap = 0;
+      FZCHK(hipMalloc((void**)&f->scratch, need * sizeof(float)));
+      f->scratch_cap = need;
+    }
+    feats = f->scratch;
+    a.feats_q8 = feats_q8;
+    a.q8_scale = scale;
+  }
   a.k = f->k;
   a.wav = wav;
   a.off = offsets;
@@ -535,7 +658,12 @@ static int featurizer_run(rnnt_featurizer* f, const float* wav, const int64_t* o
     hipLaunchKernelGGL(fz_plan_kernel, dim3(1), dim3(1024), 0, st, a);
     if (launch_logmel(a, chunks, f->own_cu_lds, st)) return fz_fail(RNNT_EDEVICE, "fz_logmel launch failed");
   }
-  if (n_pad > 0) hipLaunchKernelGGL(fz_norm_kernel, dim3(n_pad), dim3(NT), 0, st, a);
+  if (n_pad > 0) {
+    if (feats_q8)
+      hipLaunchKernelGGL(fz_norm_q8_kernel, dim3(n_pad), dim3(NT), 0, st, a);
+    else
+      hipLaunchKernelGGL(fz_norm_kernel, dim3(n_pad), dim3(NT), 0, st, a);
+  }
   FZCHK(hipGetLastError());
   return 0;
 }
@@ -545,8 +673,8 @@ extern "C" int rnnt_featurizer_run(rnnt_featurizer* f, const float* wav, const i
                                    float* feats, int32_t* feat_lens, int T_out, void* stream) {
   if (!f || !wav || !wav_lens || !wav_lens_host || !feats || !feat_lens) return fz_fail(RNNT_EINVAL, "null argument");
   if (n < 0 || n_pad < n || n_pad <= 0 || T_out <= 0) return fz_fail(RNNT_EINVAL, "bad n / n_pad / T_out");
-  return featurizer_run(f, wav, offsets, stride, wav_lens, wav_lens_host, n, n_pad, feats, nullptr, feat_lens, T_out,
-                        stream);
+  return featurizer_run(f, wav, offsets, stride, wav_lens, wav_lens_host, n, n_pad, feats, nullptr, 0.0f, nullptr,
+                        feat_lens, T_out, stream);
 }
 
 extern "C" int rnnt_featurizer_run_rows(rnnt_featurizer* f, const float* wav, const int64_t* offsets, int64_t stride,
@@ -555,6 +683,35 @@ extern "C" int rnnt_featurizer_run_rows(rnnt_featurizer* f, const float* wav, co
   if (!f || !wav || !wav_lens || !wav_lens_host || !feats || !row_off || !feat_lens)
     return fz_fail(RNNT_EINVAL, "null argument");
   if (n < 0 || max_frames <= 0) return fz_fail(RNNT_EINVAL, "bad n / max_frames");
-  return featurizer_run(f, wav, offsets, stride, wav_lens, wav_lens_host, n, n, feats, row_off, feat_lens, max_frames,
-                        stream);
+  return featurizer_run(f, wav, offsets, stride, wav_lens, wav_lens_host, n, n, feats, nullptr, 0.0f, row_off,
+                        feat_lens, max_frames, stream);
+}
+
+// scale and alignment of an int8 run's output (the engine's q8 entries need 16-byte alignment)
+static int check_q8_out(const int8_t* feats, float scale) {
+  if (!(scale > 0.0f) || !std::isfinite(scale)) return fz_fail(RNNT_EINVAL, "scale must be finite and > 0");
+  if ((uintptr_t)feats & 15) return fz_fail(RNNT_EINVAL, "int8 features must be 16-byte aligned");
+  return 0;
+}
+
+extern "C" int rnnt_featurizer_run_q8(rnnt_featurizer* f, const float* wav, const int64_t* offsets, int64_t stride,
+                                      const int32_t* wav_lens, const int32_t* wav_lens_host, int n, int n_pad,
+                                      float scale, int8_t* feats, int32_t* feat_lens, int T_out, void* stream) {
+  if (!f || !wav || !wav_lens || !wav_lens_host || !feats || !feat_lens) return fz_fail(RNNT_EINVAL, "null argument");
+  if (n < 0 || n_pad < n || n_pad <= 0 || T_out <= 0) return fz_fail(RNNT_EINVAL, "bad n / n_pad / T_out");
+  if (check_q8_out(feats, scale)) return RNNT_EINVAL;
+  return featurizer_run(f, wav, offsets, stride, wav_lens, wav_lens_host, n, n_pad, nullptr, feats, scale, nullptr,
+                        feat_lens, T_out, stream);
+}
+
+extern "C" int rnnt_featurizer_run_rows_q8(rnnt_featurizer* f, const float* wav, const int64_t* offsets,
+                                           int64_t stride, const int32_t* wav_lens, const int32_t* wav_lens_host,
+                                           int n, float scale, int8_t* feats, const int64_t* row_off,
+                                           int32_t* feat_lens, int max_frames, void* stream) {
+  if (!f || !wav || !wav_lens || !wav_lens_host || !feats || !row_off || !feat_lens)
+    return fz_fail(RNNT_EINVAL, "null argument");
+  if (n < 0 || max_frames <= 0) return fz_fail(RNNT_EINVAL, "bad n / max_frames");
+  if (check_q8_out(feats, scale)) return RNNT_EINVAL;
+  return featurizer_run(f, wav, offsets, stride, wav_lens, wav_lens_host, n, n, nullptr, feats, scale, row_off,
+                        feat_lens, max_frames, stream);
 }

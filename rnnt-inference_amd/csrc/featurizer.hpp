@@ -41,8 +41,11 @@ struct FzArgs {
   const int64_t* off;       // [n] or nullptr
   int64_t stride;
   const int32_t* wav_lens;  // [n]
-  float* feats;             // [T_out][n_pad][256], or ragged rows (row_off)
+  float* feats;             // [T_out][n_pad][256], or ragged rows (row_off); an int8 run: the fp32 scratch
   const int64_t* row_off;   // ragged output: frame t of row n at feats + (row_off[n] + t) * 240 (nullptr: padded)
+  int64_t scr_T;            // int8 run (> 0): feats is the scratch, frame t of row n at feats + (n * scr_T + t) * 240
+  int8_t* feats_q8;         // int8 run: the caller's output, [T_out][n_pad][256] or ragged rows of 240 bytes (row_off)
+  float q8_scale;           // int8 run: byte = q8(v * q8_scale)
   int32_t* feat_lens;       // [n_pad] ([n] ragged)
   int2* plan;               // [chunks] (utterance, chunk) per fz_logmel workgroup (fz_plan_kernel)
   int n, n_pad, T_out;

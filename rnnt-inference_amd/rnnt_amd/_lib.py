@@ -63,6 +63,12 @@ _SIGS = {
                                       C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "rnnt_featurizer_run_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    # the same with int8 output: the scale goes before the feature pointer
+    "rnnt_featurizer_run_q8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "rnnt_featurizer_run_rows_q8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_void_p]),
     "rnnt_engine_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "rnnt_engine_set_tile": (C.c_int, [C.c_void_p, C.c_char_p]),
     "rnnt_engine_set_decode_persist": (C.c_int, [C.c_void_p, C.c_int]),

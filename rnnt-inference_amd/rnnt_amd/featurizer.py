@@ -143,10 +143,13 @@ class FilterbankFeatures:
                    log=log, pad_out_feat=cfg.get("pad_out_feat"))
 
     def featurize(self, wav, wav_lens, wav_lens_host=None, n=None, n_pad=None, T_out=None, offsets=None,
-                  out=None, feat_lens=None, stream=None):
+                  out=None, feat_lens=None, stream=None, scale=None):
         """Native entry: wav cuda fp32 [N][stride] (zero-padded batch) or 1-D ragged storage with
         offsets (cuda int64 [n]); wav_lens cuda int32 [n].  Returns (feats [T_out][n_pad][256],
-        feat_lens [n_pad] int32) on the device -- the engine's encode input."""
+        feat_lens [n_pad] int32) on the device -- the engine's encode input.  With ``scale`` (the
+        encoding engine's ``input_scale()``) feats is int8, quantised by the featurizer's last kernel
+        (rnnt_featurizer_run_q8): the bytes ``engine.quantize`` makes of the fp32 result, zero in all
+        padding; a passed ``out`` must then be int8."""
         import torch
         if wav_lens_host is None:
             wav_lens_host = wav_lens.cpu()
@@ -156,11 +159,14 @@ class FilterbankFeatures:
         if T_out is None:
             T_out = max([feature_frames(v) for v in lh[:n]] + [1])
         dev = wav.device
+        dtype = torch.float32 if scale is None else torch.int8
         if out is None:
-            out = torch.empty((T_out, n_pad, 256), dtype=torch.float32, device=dev)
+            out = torch.empty((T_out, n_pad, 256), dtype=dtype, device=dev)
+        elif out.dtype != dtype:
+            raise ValueError(f"out must be {dtype} ({'no ' if scale is None else ''}scale given), got {out.dtype}")
         if feat_lens is None:
             feat_lens = torch.empty(n_pad, dtype=torch.int32, device=dev)
-        assert out.is_contiguous() and out.shape == (T_out, n_pad, 256) and out.dtype == torch.float32
+        assert out.is_contiguous() and out.shape == (T_out, n_pad, 256)
         assert wav.dtype == torch.float32 and wav_lens.dtype == torch.int32 and wav.is_contiguous()
         if offsets is not None:
             assert offsets.dtype == torch.int64 and offsets.numel() >= n
@@ -168,25 +174,38 @@ class FilterbankFeatures:
         else:
             assert wav.dim() == 2 and wav.shape[0] >= n
             stride = wav.shape[1]
-        _lib.check(_lib.lib().rnnt_featurizer_run(self._h, _ptr(wav), _ptr(offsets), stride, _ptr(wav_lens),
-                                                  lh.ctypes.data_as(C.c_void_p), n, n_pad, _ptr(out),
-                                                  _ptr(feat_lens), T_out, _stream_handle(stream)),
-                   "rnnt_featurizer_run")
+        if scale is None:
+            _lib.check(_lib.lib().rnnt_featurizer_run(self._h, _ptr(wav), _ptr(offsets), stride, _ptr(wav_lens),
+                                                      lh.ctypes.data_as(C.c_void_p), n, n_pad, _ptr(out),
+                                                      _ptr(feat_lens), T_out, _stream_handle(stream)),
+                       "rnnt_featurizer_run")
+        else:
+            _lib.check(_lib.lib().rnnt_featurizer_run_q8(self._h, _ptr(wav), _ptr(offsets), stride, _ptr(wav_lens),
+                                                         lh.ctypes.data_as(C.c_void_p), n, n_pad, float(scale),
+                                                         _ptr(out), _ptr(feat_lens), T_out, _stream_handle(stream)),
+                       "rnnt_featurizer_run_q8")
         return out, feat_lens
 
     def featurize_rows(self, wav, wav_lens, wav_lens_host, out, row_off, max_frames, offsets=None, feat_lens=None,
-                       stream=None):
+                       stream=None, scale=None):
         """Ragged entry for a feature store (rnnt_featurizer_run_rows): sample i's frames written as
         240-channel rows out[row_off[i] + t] (out cuda fp32 [rows][240]; row_off host int64 [n],
         bounds-checked against out here, then uploaded), nothing else touched; each sample's frames
-        <= max_frames.  Returns feat_lens cuda int32 [n]."""
+        <= max_frames.  An int8 ``out`` (rnnt_featurizer_run_rows_q8) takes ``scale``, the encoding
+        engine's ``input_scale()``, and gets the bytes ``engine.quantize`` makes of the fp32 rows.
+        Returns feat_lens cuda int32 [n]."""
         import torch
+        if out.dtype == torch.int8:
+            if scale is None:
+                raise ValueError("an int8 store needs scale= (the encoding engine's input_scale())")
+        elif scale is not None:
+            raise ValueError("scale= is for an int8 store; this one is " + str(out.dtype))
         lh = np.ascontiguousarray(np.asarray(wav_lens_host, dtype=np.int32))
         n = len(lh)
         dev = wav.device
         if feat_lens is None:
             feat_lens = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        assert out.is_contiguous() and out.dim() == 2 and out.shape[1] == 240 and out.dtype == torch.float32
+        assert out.is_contiguous() and out.dim() == 2 and out.shape[1] == 240 and out.dtype in (torch.float32, torch.int8)
         assert wav.dtype == torch.float32 and wav.is_contiguous() and wav_lens.dtype == torch.int32
         ro = np.ascontiguousarray(np.asarray(row_off, dtype=np.int64))
         if ro.shape != (n,):
@@ -204,10 +223,17 @@ class FilterbankFeatures:
         else:
             assert wav.dim() == 2 and wav.shape[0] >= n
             stride = wav.shape[1]
-        _lib.check(_lib.lib().rnnt_featurizer_run_rows(self._h, _ptr(wav), _ptr(offsets), stride, _ptr(wav_lens),
-                                                       lh.ctypes.data_as(C.c_void_p), n, _ptr(out), _ptr(row_off),
-                                                       _ptr(feat_lens), int(max_frames), _stream_handle(stream)),
-                   "rnnt_featurizer_run_rows")
+        if scale is None:
+            _lib.check(_lib.lib().rnnt_featurizer_run_rows(self._h, _ptr(wav), _ptr(offsets), stride, _ptr(wav_lens),
+                                                           lh.ctypes.data_as(C.c_void_p), n, _ptr(out), _ptr(row_off),
+                                                           _ptr(feat_lens), int(max_frames), _stream_handle(stream)),
+                       "rnnt_featurizer_run_rows")
+        else:
+            _lib.check(_lib.lib().rnnt_featurizer_run_rows_q8(self._h, _ptr(wav), _ptr(offsets), stride,
+                                                              _ptr(wav_lens), lh.ctypes.data_as(C.c_void_p), n,
+                                                              float(scale), _ptr(out), _ptr(row_off), _ptr(feat_lens),
+                                                              int(max_frames), _stream_handle(stream)),
+                       "rnnt_featurizer_run_rows_q8")
         return feat_lens
 
     def forward(self, x, x_lens, pad_batch_size):

@@ -473,6 +473,8 @@ class GpuWavQSL(_SortedQSL):
     featurizer per calling thread (its workspace is per object), on the caller's stream.
     ``lengths`` are the feature lengths (what the SUT sorts by), ``wav_lengths`` the samples."""
 
+    q8_scale = None  # quantized(): the engine's input scale; assemble then returns int8 batches
+
     def __init__(self, wavs, device="cuda", featurizer_kwargs=None):
         import torch
         from .featurizer import feature_frames
@@ -496,8 +498,21 @@ class GpuWavQSL(_SortedQSL):
             self._tls.fz = fz
         return fz
 
+    def quantized(self, engine):
+        """A view of this QSL (the same audio store, no second copy) whose ``assemble`` and
+        ``batch_inputs`` return int8 batches, written by the featurizer itself with the engine's
+        input scale (rnnt_featurizer_run_q8): a quarter of the batch's HBM bytes, no fp32 batch in
+        between.  The SUTs run on it unchanged (Engine's encode calls dispatch on the dtype) and
+        return the same tokens.  ``engine`` must be on this QSL's device."""
+        import copy
+        q = copy.copy(self)
+        q._tls = threading.local()
+        q.q8_scale = engine.input_scale()
+        return q
+
     def assemble(self, indices, n_pad=None):
-        """-> (x cuda [T_max, n_pad, 256] fp32, lens cuda int32 [n_pad], lens_host [n])."""
+        """-> (x cuda [T_max, n_pad, 256] fp32 (int8 for a ``quantized`` view), lens cuda int32 [n_pad],
+        lens_host [n])."""
         import torch
         idx = np.asarray(indices, np.int64)
         n = len(idx)
@@ -506,7 +521,7 @@ class GpuWavQSL(_SortedQSL):
         wl = self.wav_lengths[idx].astype(np.int32)
         off = torch.from_numpy(self.offsets[idx]).to(self.device)
         x, lens = self._featurizer().featurize(self.store, torch.from_numpy(wl).to(self.device), wl, n=n, n_pad=n_pad,
-                                               T_out=max(int(bl.max()), 1), offsets=off)
+                                               T_out=max(int(bl.max()), 1), offsets=off, scale=self.q8_scale)
         return x, lens, bl
 
     def batch_inputs(self, indices, n_pad, device=None):
@@ -524,7 +539,9 @@ class FeatureStore:
     no fragmentation): 2048-slot stores of 35 s samples are ~2 GB, small beside 288 GB of HBM.
     The free list is host-side; ``alloc=False`` keeps the bookkeeping alone (CPU tests)."""
 
-    def __init__(self, slots, max_frames, device="cuda", alloc=True):
+    def __init__(self, slots, max_frames, device="cuda", alloc=True, dtype=None):
+        """dtype: torch.float32 (default) or torch.int8 -- a store of int8 rows, a quarter of the bytes,
+        for a producer that writes int8 (WavFeed with q8_scale) and the engines' _q8 stream entries."""
         if int(slots) <= 0 or int(max_frames) <= 0:
             raise ValueError("a feature store needs slots > 0 and max_frames > 0")
         self.slots, self.max_frames = int(slots), int(max_frames)
@@ -534,13 +551,17 @@ class FeatureStore:
         self.feats = None
         if alloc:
             import torch
-            self.feats = torch.empty((self.slots * self.max_frames, R.trans_input_size), dtype=torch.float32,
+            if dtype not in (None, torch.float32, torch.int8):
+                raise ValueError(f"a feature store holds torch.float32 or torch.int8 rows, not {dtype}")
+            self.feats = torch.empty((self.slots * self.max_frames, R.trans_input_size), dtype=dtype or torch.float32,
                                      device=device)
 
     def quantized(self, engine):
         """A store of the same geometry and slot bookkeeping whose rows are this store's rows as int8
         (``engine.quantize``, once; a quarter of the HBM): for a store that has been filled, e.g. a
-        pre-featurized query.  The featurizer writes fp32 rows, so a WavFeed's live store stays fp32."""
+        pre-featurized query.  A live store that producers fill while consumers read is made int8 from
+        the start instead (``dtype=torch.int8``; ``WavFeed(q8_scale=...)`` writes it through the
+        featurizer's int8 rows entry)."""
         import torch
         out = FeatureStore(self.slots, self.max_frames, alloc=False)
         with self._lock:
@@ -588,8 +609,12 @@ class WavFeed:
     sizes it to the lane's engine slots + ahead); max_frames: a store slot's rows (default the
     QSL's longest sample)."""
 
-    def __init__(self, qsl, store_slots=None, pro_batch=512, ahead=None, max_frames=None, alloc=True, cu_mask=None):
+    def __init__(self, qsl, store_slots=None, pro_batch=512, ahead=None, max_frames=None, alloc=True, cu_mask=None,
+                 q8_scale=None):
+        """q8_scale: the lane's engines' ``input_scale()`` -- the store is then int8 and ``featurize``
+        writes it through rnnt_featurizer_run_rows_q8 (None: an fp32 store)."""
         self.qsl, self.pro_batch, self.ahead = qsl, int(pro_batch), ahead
+        self.q8_scale = None if q8_scale is None else float(q8_scale)
         self.cu_mask = cu_mask  # featurize on this CU set only (engine.cu_mask_words); None: any CU
         self._pstreams = []
         self.store_slots, self.alloc = store_slots, alloc
@@ -608,7 +633,11 @@ class WavFeed:
             self.ahead = int(ahead)
         if self.store is None:
             n = int(self.store_slots or slots + self.ahead)
-            self.store = FeatureStore(n, self.max_frames, device=self.qsl.device, alloc=self.alloc)
+            dtype = None
+            if self.q8_scale is not None:
+                import torch
+                dtype = torch.int8
+            self.store = FeatureStore(n, self.max_frames, device=self.qsl.device, alloc=self.alloc, dtype=dtype)
 
     def make_stream(self):
         """The producer's stream (one per feed, kept across Server instances)."""
@@ -629,7 +658,8 @@ class WavFeed:
             wld = torch.from_numpy(wl).to(dev)
             rows = np.array([self.store.row(s) for s in slots], np.int64)
             self.qsl._featurizer().featurize_rows(self.qsl.store, wld, wl, self.store.feats, rows,
-                                                  self.store.max_frames, offsets=off, stream=stream)
+                                                  self.store.max_frames, offsets=off, stream=stream,
+                                                  scale=self.q8_scale)
             stream.synchronize()
         self.batches += 1
         return self.qsl.lengths[idx]
@@ -693,6 +723,10 @@ class ServerSUT:
             if any(not np.array_equal(f.qsl.lengths, self.lengths) for f in self.feeds):
                 raise ValueError("every feed must hold the same samples")
             self.lanes = self._assign_lanes(lanes)
+            for e, f in zip(self.engines, self.lanes):  # int8 stores carry their scale in the bytes
+                s = getattr(self.feeds[f], "q8_scale", None)
+                if s is not None and e.input_scale() != s:
+                    raise ValueError(f"feed {f} quantises with scale {s}, its engine's input scale is {e.input_scale()}")
             for f in range(len(self.feeds)):
                 nl = sum(1 for x in self.lanes if x == f)
                 self.feeds[f].open(nl * self.slots, self.slots)

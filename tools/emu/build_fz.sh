@@ -18,6 +18,9 @@ anchor = '  float2(*scr)[4][SCR] = scrs[sub];\n'
 assert anchor in t, "fz_logmel_kernel LDS declarations moved: update tools/emu/build_fz.sh"
 t = t.replace(anchor, anchor + '  if (threadIdx.x == 0) { emu_fz_poison(tab, sizeof(tab)); emu_fz_poison(win, sizeof(win)); '
               'emu_fz_poison(segs, sizeof(segs)); emu_fz_poison(scrs, sizeof(scrs)); }\n')
+anchor = '  __shared__ float s_rstd[FZ_FEAT_PAD];\n'
+assert anchor in t, "fz_norm_q8_kernel LDS declarations moved: update tools/emu/build_fz.sh"
+t = t.replace(anchor, anchor + '  if (threadIdx.x == 0) { emu_fz_poison(s_mean, sizeof(s_mean)); emu_fz_poison(s_rstd, sizeof(s_rstd)); }\n')
 if 'asm volatile' in t or 'asm(' in t:
     raise SystemExit('unhandled asm in featurizer.hip')
 open(f"{out}/featurizer_emu.hip.cpp", "w").write(t)

@@ -7,10 +7,17 @@
 // a wave only meet at explicit wave / workgroup barriers here (no implicit lockstep), so a hand-off
 // between lanes that relies on lockstep instead of wave_lds_sync also shows up as a difference
 // from the float64 restatement (tools/emu/fz_emu_check.py).
-// Built by tools/emu/build_fz.sh.  Usage: fz_emu <input.bin> <output.bin>
+// Built by tools/emu/build_fz.sh.  Usage: fz_emu <input.bin> <output.bin> [scale [rows]]
 //   input:  int32 n, int32 n_pad, int32 T_out, float window[320], float fb[80*257], int32 lens[n],
 //           float wav[n][max_len] (rows zero padded to max_len = max(lens))
 //   output: int32 feat_lens[n_pad], float feats[T_out][n_pad][256]
+// With a scale (> 0) the int8 entries run instead (fz_norm_q8_kernel, its LDS poisoned too):
+//   output: int32 feat_lens[n_pad], int8 feats[T_out][n_pad][256] (rnnt_featurizer_run_q8 into an
+//           exact-size buffer of 0xA5 bytes);
+//   with "rows" as a fourth argument (rnnt_featurizer_run_rows_q8): int32 feat_lens[n],
+//           int64 row_off[n], int64 store_rows, int8 store[store_rows][240] -- a store of 0xA5
+//           bytes larger than the rows written, sample i's frames at row_off[i] (out of order,
+//           gaps between; the last sample ends at the store's last row).
 #include "emu_hip.hpp"
 
 #include <random>
@@ -44,9 +51,11 @@ int rnnt_internal_fail(int code, const std::string& msg) {
 
 int main(int argc, char** argv) {
   if (argc < 3) {
-    fprintf(stderr, "usage: fz_emu input.bin output.bin\n");
+    fprintf(stderr, "usage: fz_emu input.bin output.bin [scale [rows]]\n");
     return 2;
   }
+  const float scale = argc > 3 ? (float)atof(argv[3]) : 0.0f;
+  const bool rows = argc > 4 && std::string(argv[4]) == "rows";
   const char* pm = getenv("EMU_POISON");
   const std::string mode = pm ? pm : "nan";
   g_poison_mode = mode == "nan" ? 0 : mode == "big" ? 1 : mode == "zero" ? 2 : 3;
@@ -85,11 +94,44 @@ int main(int argc, char** argv) {
   cfg.norm_eps = 1e-12f;
   rnnt_featurizer* f = nullptr;
   if (rnnt_featurizer_create(&cfg, window.data(), fb.data(), 0, &f)) return 3;
-  if (rnnt_featurizer_run(f, wav, nullptr, maxl, d_lens, lens.data(), n, n_pad, feats, flen, T_out, nullptr)) return 3;
+  FILE* fo = nullptr;
+  if (scale > 0.0f && rows) {
+    // sample i's slot: T_out + 3 rows apart, in reversed order, 5 rows of slack in front; the last
+    // byte of the store is the last byte of sample 0's longest possible run
+    std::vector<int64_t> roff(n);
+    for (int i = 0; i < n; ++i) roff[i] = 5 + (int64_t)(n - 1 - i) * (T_out + 3);
+    const int64_t store_rows = 5 + (int64_t)(n - 1) * (T_out + 3) + rnnt_featurizer_frames(lens[0]);
+    int64_t* d_roff = (int64_t*)malloc((size_t)n * 8);
+    memcpy(d_roff, roff.data(), (size_t)n * 8);
+    int8_t* store = (int8_t*)aligned_alloc(16, ((size_t)store_rows * 240 + 15) / 16 * 16);
+    memset(store, 0xA5, (size_t)store_rows * 240);
+    if (rnnt_featurizer_run_rows_q8(f, wav, nullptr, maxl, d_lens, lens.data(), n, scale, store, d_roff, flen, T_out,
+                                    nullptr))
+      return 3;
+    fo = fopen(argv[2], "wb");
+    fwrite(flen, 4, n, fo);
+    fwrite(roff.data(), 8, n, fo);
+    fwrite(&store_rows, 8, 1, fo);
+    fwrite(store, 1, (size_t)store_rows * 240, fo);
+    free(d_roff);
+    free(store);
+  } else if (scale > 0.0f) {
+    const size_t bytes = (size_t)T_out * n_pad * 256;  // a multiple of 16
+    int8_t* q = (int8_t*)aligned_alloc(16, bytes);
+    memset(q, 0xA5, bytes);  // the kernel must write every byte
+    if (rnnt_featurizer_run_q8(f, wav, nullptr, maxl, d_lens, lens.data(), n, n_pad, scale, q, flen, T_out, nullptr))
+      return 3;
+    fo = fopen(argv[2], "wb");
+    fwrite(flen, 4, n_pad, fo);
+    fwrite(q, 1, bytes, fo);
+    free(q);
+  } else {
+    if (rnnt_featurizer_run(f, wav, nullptr, maxl, d_lens, lens.data(), n, n_pad, feats, flen, T_out, nullptr)) return 3;
+    fo = fopen(argv[2], "wb");
+    fwrite(flen, 4, n_pad, fo);
+    fwrite(feats, 4, (size_t)T_out * n_pad * 256, fo);
+  }
   rnnt_featurizer_destroy(f);
-  FILE* fo = fopen(argv[2], "wb");
-  fwrite(flen, 4, n_pad, fo);
-  fwrite(feats, 4, (size_t)T_out * n_pad * 256, fo);
   fclose(fo);
   fprintf(stderr, "fz_emu: %ld workgroups, poison %s\n", emu_workgroups, mode.c_str());
   free(wav);

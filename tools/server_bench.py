@@ -107,6 +107,9 @@ def main():
     ap.add_argument("--fz-cus", type=int, default=0,
                     help="--wav: reserve this many CUs per XCD for the featurizer and keep the engines off them "
                          "(CU-masked streams); 0: shared CUs")
+    ap.add_argument("--q8", action="store_true",
+                    help="--wav: int8 feature stores, written by the featurizer itself (WavFeed q8_scale): a quarter "
+                         "of the store's HBM and of the stream gather's read bytes")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     pm, _ = weights.build_model()
@@ -119,7 +122,9 @@ def main():
         wavs = synthetic.make_wavs(synthetic.wav_lengths_for_frames(frames, seed=args.seed), seed=args.seed,
                                    device="cuda")
         fz_mask = cu_mask_words(args.fz_cus, reserved=True) if args.fz_cus else None
-        feeds = [WavFeed(GpuWavQSL(wavs), pro_batch=args.pro_batch, cu_mask=fz_mask) for _ in range(args.feeds)]
+        q8_scale = engines[0].input_scale() if args.q8 else None
+        feeds = [WavFeed(GpuWavQSL(wavs), pro_batch=args.pro_batch, cu_mask=fz_mask, q8_scale=q8_scale)
+                 for _ in range(args.feeds)]
         del wavs
         qsl = feeds[0].qsl
     else:
@@ -173,7 +178,7 @@ def main():
     print(json.dumps({"scenario": "Server", "target_latency_ms": TARGET_LATENCY_S * 1e3, "percentile": PERCENTILE,
                       "duration_s": args.duration, "mode": args.mode, "slots_or_max_batch": args.max_batch,
                       "split_len": args.split_len if args.mode == "continuous" else None, "inflight": args.inflight,
-                      "pipelined": args.pipelined, "input": (f"wav ({args.feeds} feeds, pro_batch {args.pro_batch}, featurizer CUs/XCD {args.fz_cus or 'shared'})"
+                      "pipelined": args.pipelined, "input": (f"wav ({args.feeds} feeds, pro_batch {args.pro_batch}, featurizer CUs/XCD {args.fz_cus or 'shared'}, {'int8' if args.q8 else 'fp32'} stores)"
                                                              if args.wav else "features (GpuQSL store)"),
                       "best_valid_qps_per_gpu": best["target_qps"] if best else None, "points": points}))
     for e in engines:
