@@ -180,6 +180,23 @@ int rnnt_engine_encode_stream(rnnt_engine* e, const float* store, const int64_t*
                               const int32_t* lens_host, const int32_t* reset, int T, int n, int n_pad, void* stream);
 int rnnt_engine_decode_stream(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_res, const int32_t* reset,
                               void* stream);
+/* Detail decode: rnnt_engine_decode / rnnt_engine_decode_stream (the same res and res_len, the same
+ * argument checks) which also write, for every emitted token, at the token's position in its result
+ * row: emit_frame device int32 [n][max_res], the encoder frame (60 ms units: 10 ms hop x splicing 3 x
+ * stacking 2; counted from the start of the utterance) the row stood on when it emitted, and
+ * emit_conf device fp32 [n][max_res], the softmax probability of the emitted label over the 29 real
+ * labels, conf = 1 / sum_j exp(v_j - v_best) on the joint's fp32 logits (exact definition: DESIGN.md
+ * section 2).  Positions at or past res_len[i] are left untouched (nothing is filled).  Either pointer
+ * may be NULL (frames only: no exp and no division is executed); with both NULL the calls are the plain
+ * ones.  A detail call runs ordinary step launches to the end, whatever rnnt_engine_set_decode_persist
+ * says.  Stream form: the frames of a slot are utterance-absolute if every decode call for the slot
+ * since its reset was a detail call (at least one pointer set), otherwise unspecified.  Not covered: the
+ * pipelined rnnt_engine_decode_stream_pl, the fp32 decoder (rnnt_engine_decode_f32), the operator-level
+ * loop and the C++ TorchModel drop-in. */
+int rnnt_engine_decode_detail(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_res, int32_t* emit_frame,
+                              float* emit_conf, void* stream);
+int rnnt_engine_decode_stream_detail(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_res,
+                                     const int32_t* reset, int32_t* emit_frame, float* emit_conf, void* stream);
 /* Pipelined form of the two calls above: chunk k+1's rnnt_engine_encode_stream_pl may run (on its
  * own stream, from its own host thread) while chunk k's rnnt_engine_decode_stream_pl runs on
  * another.  Chunk k's encode copies its output to the decode side once chunk k-1's decode has read

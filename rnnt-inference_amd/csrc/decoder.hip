@@ -342,12 +342,15 @@ __global__ void __launch_bounds__(256) dec_init_kernel(DecArgs a) {
 // (TorchModel::decode zeroes symbols_added and time_idx every call, rnnt_model.hpp:95-98).  Every
 // live slot re-runs the prediction of its committed state on pre_g -- the candidate the previous
 // call already held, recomputed bit-identically (a pure function of that state).
-__global__ void __launch_bounds__(256) dec_init_stream_kernel(DecArgs a, const int32_t* __restrict__ reset) {
+// tbase (detail stream decodes, else null): the slot's frame base, zero where an utterance starts.
+__global__ void __launch_bounds__(256) dec_init_stream_kernel(DecArgs a, const int32_t* __restrict__ reset,
+                                                              int32_t* __restrict__ tbase) {
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= a.Npad) return;
   const int fl = row < a.N ? a.f_lens[row] : 0;
   DecState& s = a.s;
   if (row >= a.N || reset[row]) {
+    if (tbase) tbase[row] = 0;
     s.idx[row] = -1; s.preg[row] = SOS; s.slot[row] = 0;
     float* h = hc_part(a.hc, row, 0, 0);
     for (int k = 0; k < 4 * P; ++k) h[k] = 0.0f;
@@ -847,16 +850,27 @@ __device__ __forceinline__ void joint_load_tile(JointTile& T, const DecArgs& a, 
 // (decoder.py:137-167) to the tile state and the DecState arrays.  PS: the persistent launch stores
 // write-through, as a row's next step may run on another XCD whose L2 would otherwise write back
 // its own (newer) copy of the line first.
-template <bool PS>
-__device__ __forceinline__ void joint_argmax_update(JointTile& T, const DecArgs& a, int wave, int lane) {
+// DETAIL (the detail joints, rnnt_engine_decode_detail): an emission also writes, at the token's
+// position in res, the frame the row stands on (d.frame) and the softmax probability of the emitted
+// label over the 29 real labels (d.conf): conf = 1 / S, S = sum_j det_exp(v_j - v_best), summed as a
+// fixed balanced tree -- each of the row's 16 lanes adds its labels 2l and 2l+1 (slots 29..31 are
+// exactly 0), then an xor butterfly over offsets 1, 2, 4, 8 (fp32 addition commutes, so every lane
+// holds the same bits) -- and divided as det_sigmoid divides.  Without d.conf
+// no exp and no division runs.  A compile-time variant: the default instantiations are the code as
+// it was (dec_joint_slim_kernel has one VGPR to spare).
+template <bool PS, bool DETAIL = false>
+__device__ __forceinline__ void joint_argmax_update(JointTile& T, const DecArgs& a, int wave, int lane,
+                                                    const DecDetail d = DecDetail{nullptr, nullptr, nullptr}) {
   const DecState& s = a.s;
   const int m = 4 * wave + (lane >> 4), l2 = 2 * (lane & 15);
   float bv = 0.0f;
   int bl = -1;
+  float vj[2];
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
     const int j = l2 + e;
     const float v = ((T.Lp[0][m][j] + T.Lp[1][m][j]) + T.Lp[2][m][j]) + T.Lp[3][m][j];
+    vj[e] = v;
     if (j < NLAB && (bl < 0 || v > bv)) {
       bv = v;
       bl = j;
@@ -871,6 +885,13 @@ __device__ __forceinline__ void joint_argmax_update(JointTile& T, const DecArgs&
       bl = ol;
     }
   }
+  float conf = 0.0f;
+  if (DETAIL && d.conf) {  // uniform; bv is the row's largest logit in all 16 lanes
+    float sum = (l2 < NLAB ? det_exp(vj[0] - bv) : 0.0f) + (l2 + 1 < NLAB ? det_exp(vj[1] - bv) : 0.0f);
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) sum = sum + __shfl_xor(sum, off);
+    conf = 1.0f / sum;
+  }
   if ((lane & 15) == 0 && T.walking[m]) {
     const int row = T.rows[m], best = bl;
     if (best != BLANK && T.add_[m] != MAXSYM) {
@@ -878,6 +899,10 @@ __device__ __forceinline__ void joint_argmax_update(JointTile& T, const DecArgs&
       T.idx_[m] = id;
       st_b32<PS>(&s.idx[row], (uint32_t)id);
       if (id < a.max_res) st_b32<PS>(&a.res[(size_t)row * a.max_res + id], (uint32_t)best);
+      if (DETAIL && id < a.max_res) {  // row < N (only rows with frames are listed): inside [N][max_res] like res
+        if (d.frame) d.frame[(size_t)row * a.max_res + id] = (d.tbase ? d.tbase[row] : 0) + T.tidx[m];
+        if (d.conf) d.conf[(size_t)row * a.max_res + id] = conf;
+      }
       st_b32<PS>(&s.added[row], (uint32_t)++T.add_[m]);
       st_b32<PS>(&s.preg[row], (uint32_t)best);
       const int nsl = T.slot_[m] ^ 1;  // commit the candidate (hg, cg) as (pre_hg, pre_cg)
@@ -942,8 +967,9 @@ struct JointRegs {
   bool wl = false;
 };
 // jg / njg: this workgroup's index among the joint workgroups and their count (row tiles jg, jg + njg, ...)
-template <bool PS>
-__device__ __forceinline__ void dec_joint_body(const DecArgs& a, int parity, int jg, int njg, JointLds& L, JointRegs& W) {
+template <bool PS, bool DETAIL = false>
+__device__ __forceinline__ void dec_joint_body(const DecArgs& a, int parity, int jg, int njg, JointLds& L, JointRegs& W,
+                                               const DecDetail d = DecDetail{nullptr, nullptr, nullptr}) {
   const DecState& s = a.s;
   JointTile& T = L.T;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, c = lane & 15;
@@ -1036,7 +1062,7 @@ __device__ __forceinline__ void dec_joint_body(const DecArgs& a, int parity, int
         }
       }
       lds_barrier();
-      joint_argmax_update<PS>(T, a, wave, lane);
+      joint_argmax_update<PS, DETAIL>(T, a, wave, lane, d);
       lds_barrier();
     }
     if (wave == 0) joint_publish<PS>(T, a, parity, lane);
@@ -1045,10 +1071,12 @@ __device__ __forceinline__ void dec_joint_body(const DecArgs& a, int parity, int
   }
 }
 
-__global__ void __launch_bounds__(256) dec_joint_kernel(DecArgs a, int parity) {
+// DETAIL = true: launched by detail decodes only (d is not read otherwise)
+template <bool DETAIL>
+__global__ void __launch_bounds__(256) dec_joint_kernel(DecArgs a, int parity, DecDetail d) {
   __shared__ JointLds L;
   JointRegs W;
-  dec_joint_body<false>(a, parity, blockIdx.x, gridDim.x, L, W);
+  dec_joint_body<false, DETAIL>(a, parity, blockIdx.x, gridDim.x, L, W, d);
 }
 
 // Co-resident joint (SLIM): 9 KB of LDS and at most 112 VGPRs, so it fits beside an encoder tick
@@ -1062,7 +1090,11 @@ __global__ void __launch_bounds__(256) dec_joint_kernel(DecArgs a, int parity) {
 struct JointSlimLds {
   JointTile T;
 };
-__global__ void SLIM_BOUNDS dec_joint_slim_kernel(DecArgs a, int parity) {
+// DETAIL = true: launched by detail decodes only (d is not read otherwise); it keeps the register cap,
+// so a detail decode still runs beside an encoder.  The body stays in the kernel: moved into a device
+// function, the default instantiation takes 112 VGPRs instead of 111.
+template <bool DETAIL>
+__global__ void SLIM_BOUNDS dec_joint_slim_kernel(DecArgs a, int parity, DecDetail d) {
   __shared__ JointSlimLds L;
   JointTile& T = L.T;
   const DecState& s = a.s;
@@ -1144,7 +1176,7 @@ __global__ void SLIM_BOUNDS dec_joint_slim_kernel(DecArgs a, int parity) {
         T.Lp[wave][c][16 + 4 * q + r] = s1[r];
       }
       lds_barrier();
-      joint_argmax_update<false>(T, a, wave, lane);
+      joint_argmax_update<false, DETAIL>(T, a, wave, lane, d);
       lds_barrier();
     }
     if (wave == 0) joint_publish<false>(T, a, parity, lane);
@@ -1277,7 +1309,19 @@ __global__ void dec_finish_kernel(DecArgs a) {
   if (row < a.N) a.res_len[row] = a.s.idx[row] + 1;
 }
 
-int launch_greedy_decode(const DecArgs& a, int32_t* host_flags, hipEvent_t* evs, hipStream_t st, const int32_t* reset) {
+// a detail stream decode ends: the slot's next chunk counts its frames from here
+__global__ void __launch_bounds__(256) dec_tbase_advance_kernel(int32_t* __restrict__ tbase,
+                                                                const int32_t* __restrict__ f_lens, int N) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row < N) tbase[row] += f_lens[row];
+}
+
+int launch_greedy_decode(const DecArgs& a, int32_t* host_flags, hipEvent_t* evs, hipStream_t st, const int32_t* reset,
+                         const DecDetail* det) {
+  // detail decode: the detail joints instead of the default ones; with neither output the plain decode
+  const bool detail = det && (det->frame || det->conf);
+  const DecDetail dd = detail ? *det : DecDetail{nullptr, nullptr, nullptr};
+  if (detail && reset && !dd.tbase) return -1;
   // every buffer the step kernels address (a missing one is a host error here, not a GPU fault)
   const void* need[] = {a.F, a.f_lens, a.hc, a.G, a.PH, a.res, a.res_len, a.w.xtab, a.w.wp[0], a.w.wp[1], a.w.bih_p[1],
                         a.w.bhh_p[0], a.w.bhh_p[1], a.w.w1p, a.w.bp, a.w.w2, a.w.b2, a.s.time, a.s.added, a.s.idx,
@@ -1288,7 +1332,8 @@ int launch_greedy_decode(const DecArgs& a, int32_t* host_flags, hipEvent_t* evs,
   if (hipMemsetAsync(a.s.count, 0, 4 * sizeof(int32_t), st) != hipSuccess) return -1;
   if (reset) {
     hipLaunchKernelGGL(dec_reset_res_kernel, dim3(a.N), dim3(256), 0, st, a.res, a.max_res, reset);
-    hipLaunchKernelGGL(dec_init_stream_kernel, dim3((a.Npad + 255) / 256), dim3(256), 0, st, a, reset);
+    hipLaunchKernelGGL(dec_init_stream_kernel, dim3((a.Npad + 255) / 256), dim3(256), 0, st, a, reset,
+                       detail ? dd.tbase : (int32_t*)nullptr);
   } else {
     if (hipMemsetAsync(a.res, 0xff, (size_t)a.N * a.max_res * sizeof(int32_t), st) != hipSuccess) return -1;
     hipLaunchKernelGGL(dec_init_kernel, dim3((a.Npad + 255) / 256), dim3(256), 0, st, a);
@@ -1333,7 +1378,9 @@ int launch_greedy_decode(const DecArgs& a, int32_t* host_flags, hipEvent_t* evs,
   // persistent tail (dec_persist_kernel): once the live rows read back fit a.persist_rows, one launch
   // runs every remaining step (0 = off; at most DEC_PERSIST_MAX rows)
 #ifndef RNNT_EMU
-  const int PERSIST_ROWS = a.persist_rows < 0 ? 0 : (a.persist_rows > DEC_PERSIST_MAX ? DEC_PERSIST_MAX : a.persist_rows);
+  // (dec_persist_kernel has no detail variant: a detail decode runs step launches to the end)
+  const int PERSIST_ROWS =
+      detail || a.persist_rows < 0 ? 0 : (a.persist_rows > DEC_PERSIST_MAX ? DEC_PERSIST_MAX : a.persist_rows);
   static std::atomic<uint64_t> ps_attr{0};
 #else
   constexpr int PERSIST_ROWS = 0;
@@ -1393,10 +1440,14 @@ int launch_greedy_decode(const DecArgs& a, int32_t* host_flags, hipEvent_t* evs,
       else
         hipLaunchKernelGGL(dec_g_kernel, dim3(xcd_grid_size(J / (16 * (G_THREADS / 64)), rg_g)), dim3(G_THREADS), 0, st, a,
                            p);
-      if (SLIM & 8)
-        hipLaunchKernelGGL(dec_joint_slim_kernel, dim3(rg_joint), dim3(256), 0, st, a, p);
+      if (detail && (SLIM & 8))
+        hipLaunchKernelGGL(dec_joint_slim_kernel<true>, dim3(rg_joint), dim3(256), 0, st, a, p, dd);
+      else if (detail)
+        hipLaunchKernelGGL(dec_joint_kernel<true>, dim3(rg_joint), dim3(256), 0, st, a, p, dd);
+      else if (SLIM & 8)
+        hipLaunchKernelGGL(dec_joint_slim_kernel<false>, dim3(rg_joint), dim3(256), 0, st, a, p, dd);
       else
-        hipLaunchKernelGGL(dec_joint_kernel, dim3(rg_joint), dim3(256), 0, st, a, p);
+        hipLaunchKernelGGL(dec_joint_kernel<false>, dim3(rg_joint), dim3(256), 0, st, a, p, dd);
     }
     // poll the live-row count one chunk behind, so the host never drains the queue: the length of
     // the live list the chunk's last joint wrote (parity step & 1; the next step's G kernel resets
@@ -1420,6 +1471,8 @@ int launch_greedy_decode(const DecArgs& a, int32_t* host_flags, hipEvent_t* evs,
     ++chunk;
   }
   hipLaunchKernelGGL(dec_finish_kernel, dim3((a.N + 255) / 256), dim3(256), 0, st, a);
+  if (detail && reset)
+    hipLaunchKernelGGL(dec_tbase_advance_kernel, dim3((a.N + 255) / 256), dim3(256), 0, st, dd.tbase, a.f_lens, a.N);
   return hipGetLastError() == hipSuccess ? step : -1;
 }
 

@@ -47,6 +47,15 @@ struct DecArgs {
   int persist_rows;        // live rows at or below which one persistent launch runs the rest (0 = off, <= DEC_PERSIST_MAX)
 };
 
+// Detail decode (rnnt_engine_decode_detail): what the joint writes beside each emitted token, at the
+// token's position in res.  Either output may be null (frames only: no exp, no division).  A kernel
+// argument of the detail joints only: the default step kernels' arguments are DecArgs as before.
+struct DecDetail {
+  int32_t* frame;          // [N][max_res] encoder frame the row stood on (tbase[row] + its frame in this call)
+  float* conf;             // [N][max_res] softmax probability of the emitted label
+  int32_t* tbase;          // [Npad] stream slots: frames decoded since the slot's reset; null (Offline): 0
+};
+
 // F = b_t + bf16(f) . W1t^T for every frame t < Tp and row tile holding a row with f_len > t
 // (fbf: the encoder output as bf16 [Tp][Npad][1024], natural k).
 int launch_joint_trans(const DecWeights& w, const uint16_t* fbf, const int32_t* f_lens, float* F, int Tp,
@@ -58,7 +67,10 @@ int launch_dec_xtab(const DecWeights& w, float* xtab, hipStream_t st);
 // Returns the number of steps enqueued (>= 0) or -1.
 // reset != nullptr: Server continuous batching -- slots keep their greedy state across calls and
 // reset[row] != 0 starts a new utterance in that slot (dec_init_stream_kernel).
+// det != nullptr with an output set: the detail joints run every step (no persistent tail, whatever
+// a.persist_rows says); with reset, det->tbase is zeroed for the reset slots and advanced by f_lens
+// when the decode ends.
 int launch_greedy_decode(const DecArgs& a, int32_t* host_flags, hipEvent_t* evs, hipStream_t st,
-                         const int32_t* reset = nullptr);
+                         const int32_t* reset = nullptr, const DecDetail* det = nullptr);
 
 }  // namespace rnnt

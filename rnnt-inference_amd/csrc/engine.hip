@@ -69,6 +69,7 @@ struct rnnt_engine {
   float *F = nullptr, *hc = nullptr, *G = nullptr, *PH = nullptr;
   int32_t* flen = nullptr;
   DecState ds{};
+  int32_t* tbase = nullptr;  // [np_max] detail stream decodes: frames each slot decoded since its reset (DecDetail)
   int32_t* host_flags = nullptr;
   hipEvent_t poll_ev[2] = {nullptr, nullptr};
   // last encoded batch
@@ -349,6 +350,8 @@ static int alloc_workspace(rnnt_engine* e) {
   r = r ? r : dev_alloc(e, &e->ds.count, 4);
   r = r ? r : dev_alloc(e, &e->ds.unfinished, 4);
   r = r ? r : dev_alloc(e, &e->ds.pc, 8);
+  r = r ? r : dev_alloc(e, &e->tbase, NP);
+  if (!r && hipMemset(e->tbase, 0, NP * sizeof(int32_t)) != hipSuccess) r = fail(RNNT_EDEVICE, "hipMemset failed");
   if (!r && hipHostMalloc((void**)&e->host_flags, 4 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
     r = fail(RNNT_ENOMEM, "hipHostMalloc failed");
   for (int i = 0; i < 2 && !r; ++i)
@@ -1051,7 +1054,7 @@ extern "C" int rnnt_engine_encode_stream_q8(rnnt_engine* e, const int8_t* store,
 }
 
 static int decode_impl(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_res, void* stream,
-                       const int32_t* reset);
+                       const int32_t* reset, int32_t* emit_frame = nullptr, float* emit_conf = nullptr);
 extern "C" int rnnt_engine_decode(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_res, void* stream) {
   return decode_impl(e, res, res_len, max_res, stream, nullptr);
 }
@@ -1060,6 +1063,17 @@ extern "C" int rnnt_engine_decode_stream(rnnt_engine* e, int32_t* res, int32_t* 
   if (!reset) return fail(RNNT_EINVAL, "decode_stream needs the reset flags");
   return decode_impl(e, res, res_len, max_res, stream, reset);
 }
+// detail decodes: the same calls with the per-token outputs (either may be null; both null: the plain decode)
+extern "C" int rnnt_engine_decode_detail(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_res,
+                                         int32_t* emit_frame, float* emit_conf, void* stream) {
+  return decode_impl(e, res, res_len, max_res, stream, nullptr, emit_frame, emit_conf);
+}
+extern "C" int rnnt_engine_decode_stream_detail(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_res,
+                                                const int32_t* reset, int32_t* emit_frame, float* emit_conf,
+                                                void* stream) {
+  if (!reset) return fail(RNNT_EINVAL, "decode_stream needs the reset flags");
+  return decode_impl(e, res, res_len, max_res, stream, reset, emit_frame, emit_conf);
+}
 
 // The decode of one encoded batch / chunk: joint_trans of its final-layer output fbf (T frames
 // before stacking, n rows of n_pad) with lengths flen, then the greedy loop; after_jt runs on the
@@ -1067,7 +1081,7 @@ extern "C" int rnnt_engine_decode_stream(rnnt_engine* e, int32_t* res, int32_t* 
 template <class AfterJT>
 static int decode_core(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_res, hipStream_t st,
                        const int32_t* reset, const uint16_t* fbf, const int32_t* flen, int T, int n, int n_pad,
-                       AfterJT after_jt) {
+                       AfterJT after_jt, const DecDetail* det = nullptr) {
   const int Tp = (T + 1) / 2;
   hipEvent_t ev0 = e->prof ? new_event(st) : nullptr;
   if (launch_joint_trans(e->dw, fbf, flen, e->F, Tp, n_pad, st))
@@ -1090,7 +1104,7 @@ static int decode_core(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_r
   a.s = e->ds;
   a.max_iter = Tp * (MAXSYM + 1) + 2;  // every step emits or advances; <= 30 emits per frame
   a.persist_rows = e->persist_rows;
-  const int steps = launch_greedy_decode(a, e->host_flags, e->poll_ev, st, reset);
+  const int steps = launch_greedy_decode(a, e->host_flags, e->poll_ev, st, reset, det);
   if (steps == -2)  // dec_persist_kernel needs its 48 + nj workgroups co-resident (rnnt_engine_set_decode_persist)
     return fail(RNNT_EDEVICE, "persistent decode timed out: its workgroups were not all resident (other kernels held "
                               "the CUs); turn the persistent tail off or give the engine the GPU");
@@ -1102,7 +1116,7 @@ static int decode_core(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_r
 }
 
 static int decode_impl(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_res, void* stream,
-                       const int32_t* reset) {
+                       const int32_t* reset, int32_t* emit_frame, float* emit_conf) {
   if (!e || !res || !res_len) return fail(RNNT_EINVAL, "null argument");
   if (e->last_n <= 0) return fail(RNNT_EINVAL, "decode before encode");
   if (!e->xtab_ok || !e->joint1_loaded || !e->joint2_loaded)
@@ -1112,8 +1126,9 @@ static int decode_impl(rnnt_engine* e, int32_t* res, int32_t* res_len, int max_r
   hipStream_t st = pick(e, stream);
   int r = state_acquire(e, st);
   if (r) return r;
+  const DecDetail det{emit_frame, emit_conf, reset ? e->tbase : nullptr};  // Offline: frame base 0
   r = decode_core(e, res, res_len, max_res, st, reset, e->fbf, e->flen, e->last_T, e->last_n, e->last_npad,
-                  [] { return 0; });
+                  [] { return 0; }, emit_frame || emit_conf ? &det : nullptr);
   return r ? r : state_release(e, st);
 }
 

@@ -88,6 +88,11 @@ _SIGS = {
     "rnnt_engine_encode_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rnnt_engine_decode_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    # detail decodes: the plain signatures with emit_frame / emit_conf before the stream
+    "rnnt_engine_decode_detail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "rnnt_engine_decode_stream_detail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "rnnt_engine_encode_stream_pl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rnnt_engine_decode_stream_pl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,

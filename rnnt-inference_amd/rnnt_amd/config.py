@@ -23,6 +23,8 @@ class RNNTParam:
     BLANK = 28
     max_symbols_per_step = 30
     sample_rate = 16000
+    hop_length = 160  # samples between feature frames (10 ms; featurizer.SUPPORTED)
+    frame_splicing = 3  # feature frames spliced into one encoder input (trans_input_size = 80 mel x 3)
     # csrc/metadata.hpp:31-33
     MAX_WAV_LEN = 240000
     MAX_FEA_LEN = 500
@@ -48,6 +50,11 @@ def seq_to_sen(seq, seq_len):
 def encoder_frames(feature_len):
     """f_lens = ceil(x_lens / stack_time_factor) (decoder.py:185, rnnt_model.hpp:88-89)."""
     return (int(feature_len) + RNNTParam.stack_time_factor - 1) // RNNTParam.stack_time_factor
+
+
+# seconds of audio per encoder output frame (the unit of a detail decode's emission frames):
+# 10 ms hop x splicing 3 x time stacking 2 = 0.06 s
+FRAME_SECONDS = RNNTParam.hop_length * RNNTParam.frame_splicing * RNNTParam.stack_time_factor / RNNTParam.sample_rate
 
 
 def encoder_ops(T):

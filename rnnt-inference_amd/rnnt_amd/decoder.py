@@ -44,18 +44,33 @@ class GreedyDecoder:
             if not self.enable_bf16:
                 self.engine.load_f32_decoder(model.pm32)
 
-    def __call__(self, x, x_lens):
-        return self.forward(x, x_lens)
+    def __call__(self, x, x_lens, details=False):
+        return self.forward(x, x_lens, details)
 
-    def forward(self, x, x_lens):
-        """x: fp32 [T, N, 240|256] (cuda), x_lens: [N] -> (res [N, 30*max_len], res_len [N])."""
+    def forward(self, x, x_lens, details=False):
+        """x: fp32 [T, N, 240|256] (cuda), x_lens: [N] -> (res [N, 30*max_len], res_len [N]).
+        details=True (the bf16 prediction / joint: not the fp32 decoder) -> (res, res_len, frames,
+        conf): per utterance, trimmed to its res_len, the tokens' emission frames (int32 tensor,
+        ``config.FRAME_SECONDS`` units) and confidences (fp32 tensor); ``timing.word_timings`` turns
+        a row into word timestamps."""
         import numpy as np
         import torch
         N = x_lens.shape[0]
         width = R.max_symbols_per_step * int(x_lens.max().item())
+        if details and not self.enable_bf16:
+            raise RuntimeError("details=True is served by the bf16 prediction / joint, not by the fp32 decoder")
+        fr = cf = None
+        if details:
+            fr = torch.zeros((N, self.engine.max_res), dtype=torch.int32, device=x.device)
+            cf = torch.zeros((N, self.engine.max_res), dtype=torch.float32, device=x.device)
         if self.run_mode == "quant":
             ops.transcription(x, x_lens, f_out=False)
-            res, rl = ops.greedy_decode(N)
+            if details:
+                res = torch.empty((N, self.engine.max_res), dtype=torch.int32, device=x.device)
+                rl = torch.empty(N, dtype=torch.int32, device=x.device)
+                self.engine.decode(res, rl, frames=fr, conf=cf)
+            else:
+                res, rl = ops.greedy_decode(N)
         else:
             T = x.shape[0]
             n_pad = pad_batch(N)
@@ -67,14 +82,18 @@ class GreedyDecoder:
             rl = torch.empty(N, dtype=torch.int32, device=x.device)
             self.engine.encode_f32(xin, lens, N)
             if self.enable_bf16:
-                self.engine.decode(res, rl)
+                self.engine.decode(res, rl, frames=fr, conf=cf)
             else:
                 self.engine.decode_f32(res, rl)
         dt = torch.int32 if self.run_mode == "quant" else torch.int64
         out = torch.full((N, width), R.SOS, dtype=dt, device=res.device)
         w = min(width, res.shape[1])
         out[:, :w] = res[:, :w].to(dt)
-        return out, rl.to(dt)
+        if not details:
+            return out, rl.to(dt)
+        lens = [min(int(k), w) for k in rl.cpu().tolist()]
+        return (out, rl.to(dt), [fr[i, :k].clone() for i, k in enumerate(lens)],
+                [cf[i, :k].clone() for i, k in enumerate(lens)])
 
     def close(self):
         self.engine.close()

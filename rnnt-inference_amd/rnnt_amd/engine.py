@@ -140,12 +140,28 @@ class Engine:
                                        T, n, n_pad, _stream_handle(stream))
         _lib.check(rc, entry)
 
-    def decode_stream(self, res, res_len, reset, stream=None):
+    @staticmethod
+    def _check_detail(res, frames, conf):
+        import torch
+        for t, dt, name in ((frames, torch.int32, "frames"), (conf, torch.float32, "conf")):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != tuple(res.shape) or not t.is_contiguous()
+                                  or t.device != res.device):
+                raise TypeError(f"{name} must be a contiguous {dt} tensor of res's shape {tuple(res.shape)} on its device")
+
+    def decode_stream(self, res, res_len, reset, stream=None, frames=None, conf=None):
         """Greedy decode of the last stream chunk, carrying each slot's prediction state and result
-        row (res cuda int32 [n, max_res], the same buffer every call); reset as for encode_stream."""
-        rc = self._lib.rnnt_engine_decode_stream(self._h, _ptr(res), _ptr(res_len), res.shape[1], _ptr(reset),
-                                                 _stream_handle(stream))
-        _lib.check(rc, "rnnt_engine_decode_stream")
+        row (res cuda int32 [n, max_res], the same buffer every call); reset as for encode_stream.
+        frames / conf: as for ``decode`` (the same buffers every call); a slot's frames count from the
+        start of its utterance when every decode_stream call since its reset passed frames or conf."""
+        if frames is None and conf is None:
+            rc = self._lib.rnnt_engine_decode_stream(self._h, _ptr(res), _ptr(res_len), res.shape[1], _ptr(reset),
+                                                     _stream_handle(stream))
+            _lib.check(rc, "rnnt_engine_decode_stream")
+            return
+        self._check_detail(res, frames, conf)
+        rc = self._lib.rnnt_engine_decode_stream_detail(self._h, _ptr(res), _ptr(res_len), res.shape[1], _ptr(reset),
+                                                        _ptr(frames), _ptr(conf), _stream_handle(stream))
+        _lib.check(rc, "rnnt_engine_decode_stream_detail")
 
     def encode_stream_pl(self, store, offsets, lens, lens_host, reset, T, n, n_pad, stream=None):
         """Pipelined encode_stream (rnnt_engine_encode_stream_pl): chunk k+1's encode runs while
@@ -166,10 +182,19 @@ class Engine:
                                                     _stream_handle(stream))
         _lib.check(rc, "rnnt_engine_decode_stream_pl")
 
-    def decode(self, res, res_len, stream=None):
-        """res: cuda int32 [n, max_res]; res_len: cuda int32 [n]."""
-        rc = self._lib.rnnt_engine_decode(self._h, _ptr(res), _ptr(res_len), res.shape[1], _stream_handle(stream))
-        _lib.check(rc, "rnnt_engine_decode")
+    def decode(self, res, res_len, stream=None, frames=None, conf=None):
+        """res: cuda int32 [n, max_res]; res_len: cuda int32 [n].  frames (cuda int32) / conf (cuda
+        fp32), both of res's shape and each optional: per emitted token, at its position in res, the
+        encoder frame (``config.FRAME_SECONDS`` units) it was emitted on and the softmax probability
+        of the label; positions at or past res_len are left as they were."""
+        if frames is None and conf is None:
+            rc = self._lib.rnnt_engine_decode(self._h, _ptr(res), _ptr(res_len), res.shape[1], _stream_handle(stream))
+            _lib.check(rc, "rnnt_engine_decode")
+            return
+        self._check_detail(res, frames, conf)
+        rc = self._lib.rnnt_engine_decode_detail(self._h, _ptr(res), _ptr(res_len), res.shape[1], _ptr(frames),
+                                                 _ptr(conf), _stream_handle(stream))
+        _lib.check(rc, "rnnt_engine_decode_detail")
 
     def infer(self, feats, lens, lens_host, res, res_len, n=None, stream=None):
         T, n_pad, _ = feats.shape

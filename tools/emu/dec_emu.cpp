@@ -1,8 +1,12 @@
 // dec_emu.cpp -- runs the engine's greedy decode (decoder.hip: launch_dec_xtab +
 // launch_greedy_decode, every step kernel) on the host emulation of the wave model
 // (emu_hip.hpp) and compares tokens with the oracle (oracle_greedy_decode, bf16 mode).
-// Built with AddressSanitizer by tools/emu/build.sh.  Usage: dec_emu [N rows] [Tp] [seed] [server] [blank bias]
+// Built with AddressSanitizer by tools/emu/build.sh.  Usage: dec_emu [N rows] [Tp] [seed] [server] [blank bias] [detail]
 // (server: two decode_stream-style calls over halves of the frames, slots kept between them).
+// detail != 0 (sixth argument; without it the run and its output are as before): the detail joints
+// (rnnt_engine_decode_detail) run instead of the default ones, and the per-token emission frames and
+// confidences are compared bit for bit with a host replay of the greedy loop over oracle_prediction,
+// oracle_joint and oracle_exp -- two more lines, "frames identical" and "conf identical".
 #include "emu_hip.hpp"
 #include "decoder_emu.hip.cpp"
 
@@ -14,8 +18,33 @@ extern "C" void oracle_greedy_decode(int Tp, int N, const float* f, const int32_
                                      const float* const* pbih, const float* const* pbhh, const float* W1t,
                                      const float* W1p, const float* bt, const float* bp, const float* W2,
                                      const float* b2, int32_t* res, int32_t* res_len, int max_res, int32_t* steps);
+extern "C" void oracle_joint(int N, const float* f, const float* g, int bf16, const float* W1t, const float* W1p,
+                             const float* bt, const float* bp, const float* W2, const float* b2, float* logits);
+extern "C" void oracle_prediction(int N, const int32_t* pre_g, const float* h, const float* c, int bf16,
+                                  const float* embed, const float* const* pWih, const float* const* pWhh,
+                                  const float* const* pbih, const float* const* pbhh, float* g_out, float* h_out,
+                                  float* c_out);
+extern "C" float oracle_exp(float x);
 
 using namespace rnnt;
+
+// The detail decode's confidence, restated: 1 / S with S = sum over the 29 labels of
+// oracle_exp(v_j - v_best), summed as the joint sums it -- lane l of 16 adds labels 2l and 2l+1 (slots
+// 29..31 are 0), then an xor butterfly over offsets 1, 2, 4, 8 (lane 0's value).
+static float detail_conf(const float* v, int best) {
+  float s[16];
+  for (int l = 0; l < 16; ++l) {
+    const float e0 = 2 * l < NLAB ? oracle_exp(v[2 * l] - v[best]) : 0.0f;
+    const float e1 = 2 * l + 1 < NLAB ? oracle_exp(v[2 * l + 1] - v[best]) : 0.0f;
+    s[l] = e0 + e1;
+  }
+  for (int off = 1; off < 16; off <<= 1) {
+    float t[16];
+    for (int l = 0; l < 16; ++l) t[l] = s[l] + s[l ^ off];
+    memcpy(s, t, sizeof(s));
+  }
+  return 1.0f / s[0];
+}
 
 static uint16_t f2bf_bits(float f) {  // RNE
   uint32_t u;
@@ -38,6 +67,7 @@ int main(int argc, char** argv) {
   const int Tp = argc > 2 ? atoi(argv[2]) : 12;
   const int seed = argc > 3 ? atoi(argv[3]) : 1;
   const bool server = argc > 4 && atoi(argv[4]) != 0;
+  const bool detail = argc > 6 && atoi(argv[6]) != 0;
   const int Npad = (N + 31) / 32 * 32;
   const int max_res = Tp * 30 + 1;
   std::mt19937 rng(seed);
@@ -160,8 +190,16 @@ int main(int argc, char** argv) {
   int32_t host_flags[4] = {0, 0, 0, 0};
   hipEvent_t evs[2] = {nullptr, nullptr};
   int steps = 0;
+  // detail outputs: exact-size buffers, 0xA5 where nothing is written
+  DecDetail dd{nullptr, nullptr, nullptr};
+  if (detail) {
+    dd.frame = dalloc<int32_t>((size_t)N * max_res);
+    dd.conf = dalloc<float>((size_t)N * max_res);
+    if (server) dd.tbase = dalloc<int32_t>(Npad);
+  }
+  const DecDetail* det = detail ? &dd : nullptr;
   if (!server) {
-    steps = launch_greedy_decode(a, host_flags, evs, nullptr, nullptr);
+    steps = launch_greedy_decode(a, host_flags, evs, nullptr, nullptr, det);
   } else {  // Server continuous batching: two calls over the two halves of the frames, state carried
     const int T1 = (Tp + 1) / 2;
     int32_t* reset = dalloc<int32_t>(Npad);
@@ -172,14 +210,14 @@ int main(int argc, char** argv) {
     }
     a.f_lens = cl;
     a.max_iter = T1 * (MAXSYM + 1) + 2;
-    steps = launch_greedy_decode(a, host_flags, evs, nullptr, reset);
+    steps = launch_greedy_decode(a, host_flags, evs, nullptr, reset, det);
     for (int n = 0; n < Npad; ++n) {
       reset[n] = 0;
       cl[n] = std::max(flen[n] - T1, 0);
     }
     a.F = d_F + (size_t)T1 * Npad * J;
     a.max_iter = (Tp - T1) * (MAXSYM + 1) + 2;
-    steps += launch_greedy_decode(a, host_flags, evs, nullptr, reset);
+    steps += launch_greedy_decode(a, host_flags, evs, nullptr, reset, det);
   }
   printf("emulated decode: %d steps, %ld workgroups\n", steps, emu_workgroups);
 #ifdef EMU_HAS_DEC_CHECK
@@ -208,5 +246,60 @@ int main(int argc, char** argv) {
     }
   }
   printf("rows %d, emitted %d, mismatched rows %d -> %s\n", N, emitted, bad, bad ? "MISMATCH" : "tokens identical");
-  return bad ? 1 : 0;
+  if (!detail) return bad ? 1 : 0;
+  // host replay of the greedy loop (decoder.py:125-167) recording (frame, conf) per token: a blank, or a
+  // forced advance after MAXSYM symbols, moves to the next frame and keeps the prediction; an emission
+  // commits the candidate state
+  int bad_f = 0, bad_c = 0, bad_t = 0, bad_s = 0;
+  for (int n = 0; n < N; ++n) {
+    std::vector<float> h(2 * P, 0.0f), c(2 * P, 0.0f), hn(2 * P), cn(2 * P), g(P);
+    float logits[NLAB];
+    int32_t pre_g = SOS;
+    int time = 0, added = 0, idx = -1;
+    bool cand = false;
+    while (time < flen[n]) {
+      if (!cand) {
+        oracle_prediction(1, &pre_g, h.data(), c.data(), 1, embed.data(), pWih, pWhh, pbih, pbhh, g.data(), hn.data(),
+                          cn.data());
+        cand = true;
+      }
+      oracle_joint(1, f.data() + ((size_t)time * N + n) * H, g.data(), 1, W1t.data(), W1p.data(), bt.data(), bp.data(),
+                   W2.data(), b2.data(), logits);
+      int best = 0;
+      for (int j = 1; j < NLAB; ++j)
+        if (logits[j] > logits[best]) best = j;
+      if (best != BLANK && added != MAXSYM) {
+        ++idx;
+        if (idx < max_res) {
+          const size_t at = (size_t)n * max_res + idx;
+          const float cf = detail_conf(logits, best);
+          bad_t += ro[at] != best;
+          bad_f += dd.frame[at] != time;
+          bad_c += memcmp(&dd.conf[at], &cf, 4) != 0;
+          if ((dd.frame[at] != time || memcmp(&dd.conf[at], &cf, 4)) && bad_f + bad_c <= 5)
+            printf("row %d token %d: frame %d vs %d, conf %.9g vs %.9g\n", n, idx, dd.frame[at], time, dd.conf[at], cf);
+        }
+        ++added;
+        pre_g = best;
+        h = hn;
+        c = cn;
+        cand = false;
+      } else {
+        ++time;
+        added = 0;
+      }
+    }
+    bad_t += idx + 1 != rlo[n];
+    // nothing is written at or past res_len
+    for (int i = std::min(std::max(a.res_len[n], 0), max_res); i < max_res; ++i) {
+      const size_t at = (size_t)n * max_res + i;
+      const uint32_t cb = __float_as_uint(dd.conf[at]);
+      bad_s += (uint32_t)dd.frame[at] != 0xA5A5A5A5u || cb != 0xA5A5A5A5u;
+    }
+  }
+  printf("replay vs oracle tokens: %s\n", bad_t ? "MISMATCH" : "ok");
+  printf("frames: %d mismatched -> %s\n", bad_f, bad_f ? "MISMATCH" : "frames identical");
+  printf("conf: %d mismatched -> %s\n", bad_c, bad_c ? "MISMATCH" : "conf identical");
+  printf("positions past res_len: %s\n", bad_s ? "WRITTEN" : "untouched");
+  return bad || bad_f || bad_c || bad_t || bad_s ? 1 : 0;
 }
