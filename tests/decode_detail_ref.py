@@ -8,7 +8,8 @@ stood on and the confidence DESIGN.md section 2 defines:
 summed as a fixed balanced tree -- "lane" l of 16 adds labels 2l and 2l+1 (slots 29..31 are exactly
 0), then an xor butterfly over offsets 1, 2, 4, 8.  A plain module (not a conftest): the GPU tests
 and the seed choice share it.  Its tokens must equal oracle.greedy_decode's, which ties it to the
-committed oracle."""
+committed oracle.  replay_steps / replay_decode also return every step's 29 logits (the edge-model
+tests read them)."""
 import ctypes as C
 
 import numpy as np
@@ -35,6 +36,25 @@ def replay(oracle, pm, f, f_lens, max_res):
     """f [Tp, N, 1024] float32 (the restatement's encoder output), f_lens [N] ->
     (tokens, frames, conf): per row, int32 / int32 / float32 arrays of the row's res_len entries.
     Rows advance in lock step, so each step is one batched prediction and one batched joint."""
+    return _walk(oracle, pm, f, f_lens, max_res)[:3]
+
+
+def replay_steps(oracle, pm, f, f_lens, max_res):
+    """replay's (tokens, frames, conf) + (logits, emitted): per row, every joint evaluation of the
+    row in order -- logits float32 [steps, 29] and emitted int32 [steps], the label the step emitted
+    (also when the token fell past max_res) or -1 where the row advanced (a blank, or the advance
+    forced after MAXSYM symbols).  What the edge-model tests (joint_edge_models.py) read to show
+    that a decode reached its edge."""
+    return _walk(oracle, pm, f, f_lens, max_res)[:5]
+
+
+def replay_decode(oracle, pm, f, f_lens, max_res):
+    """replay_steps' five + (res, res_len) of the oracle.greedy_decode call the replay checks its tokens
+    against (res [N, max_res] with the -1 fill; res_len = res_idx + 1, which counts tokens past max_res)."""
+    return _walk(oracle, pm, f, f_lens, max_res)
+
+
+def _walk(oracle, pm, f, f_lens, max_res):
     f = np.ascontiguousarray(f, np.float32)
     f_lens = np.asarray(f_lens, np.int32)
     N = f.shape[1]
@@ -48,6 +68,7 @@ def replay(oracle, pm, f, f_lens, max_res):
     cand = np.zeros(N, bool)
     live = f_lens > 0
     toks, frs, cfs = [[] for _ in range(N)], [[] for _ in range(N)], [[] for _ in range(N)]
+    lgs, ems = [[] for _ in range(N)], [[] for _ in range(N)]
     while live.any():
         need = np.flatnonzero(live & ~cand)
         if len(need):
@@ -59,6 +80,8 @@ def replay(oracle, pm, f, f_lens, max_res):
         for k, n in enumerate(rows):
             v = logits[k]
             best = int(np.argmax(v))  # the first maximum, as torch.argmax
+            lgs[n].append(v.copy())
+            ems[n].append(best if best != BLANK and added[n] != MAXSYM else -1)
             if best != BLANK and added[n] != MAXSYM:
                 if len(toks[n]) < max_res:
                     toks[n].append(best)
@@ -75,6 +98,8 @@ def replay(oracle, pm, f, f_lens, max_res):
                     live[n] = False
     ro, rlo, _ = oracle.greedy_decode(pm, f, f_lens, max_res=max_res)
     for n in range(N):
-        assert len(toks[n]) == rlo[n] and np.array_equal(toks[n], ro[n, : rlo[n]]), f"replay tokens differ, row {n}"
+        k = min(int(rlo[n]), max_res)  # res_len = res_idx + 1 counts the tokens that fell past max_res too
+        assert len(toks[n]) == k and np.array_equal(toks[n], ro[n, :k]), f"replay tokens differ, row {n}"
     return ([np.asarray(t, np.int32) for t in toks], [np.asarray(t, np.int32) for t in frs],
-            [np.asarray(t, np.float32) for t in cfs])
+            [np.asarray(t, np.float32) for t in cfs],
+            [np.asarray(t, np.float32).reshape(-1, NLAB) for t in lgs], [np.asarray(t, np.int32) for t in ems], ro, rlo)
