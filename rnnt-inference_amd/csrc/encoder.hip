@@ -19,7 +19,7 @@
 
 namespace rnnt {
 
-// sigma table of the cell (tools/gen_act_table.py), copied to LDS by every workgroup
+// sigma table of the cell (tools/gen_act_table.py), DMA'd to LDS by every workgroup
 __device__ const __attribute__((aligned(16))) float2 g_act_tab[ENC_TAB_N] = {
 #include "act_table.inc"
 };
@@ -131,7 +131,14 @@ struct TileCfg {
   static_assert(NGT % 8 == 0, "one-batch-tile jobs deal their gate tiles to 8 XCDs");
   static_assert(BM >= 64 && BN >= 128, "one A piece (8 rows) per wave at least");
   static_assert(SMEM <= 160 * 1024, "LDS budget");
-  static_assert(BN * CROW + BN * HP <= STAGE, "c and h images share one stage buffer");
+  // the cell's fixed inputs ride with the cell state into the same buffer, past the c and h images:
+  // the tile's BM bias floats and (StackTime jobs) its BN row lengths, as 256-byte DMA pieces
+  static constexpr int BQ_OFF = BN * CROW + BN * HP, LENS_OFF = BQ_OFF + BM * 4;
+  static constexpr int BQ_PIECES = BM / 64, LENS_PIECES = BN / 64;
+  static_assert(LENS_OFF + BN * 4 <= STAGE, "c and h images, bias and lengths share one stage buffer");
+  static_assert(BQ_OFF % 16 == 0, "bias rows are read 16 bytes at a time");
+  static_assert(BQ_PIECES + LENS_PIECES <= NWAVE, "one bias or length piece per wave at most");
+  static_assert(ENC_TAB_N * 8 % (NWAVE * 1024) == 0, "sigma table: whole 1 KiB DMA pieces per wave");
   static constexpr int CPIECES = BN * CPR / 64;   // 1 KiB DMA pieces of the tile's fp16 cell state
   static_assert(CPIECES % NWAVE == 0 || CPIECES < NWAVE, "c DMA pieces per wave");
 };
@@ -296,6 +303,10 @@ __device__ __forceinline__ void lstm_i8_step(const EncStepArgs& a, int mt, int n
   const int cbuf = (nS % NBUF) * STAGE;
   const __amdgpu_buffer_rsrc_t rsC =
       __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.c + (size_t)n0 * H + (m0 >> 2)), (short)0, 0x7ffffff0, 0x00020000);
+  // with it, into the room past the c and h images (TileCfg::BQ_OFF): the tile's BM bias floats and,
+  // for a StackTime job, its BN row lengths -- 256-byte pieces (64 lanes x 4 B), wave w < BQ_PIECES
+  // one of the bias, the next LENS_PIECES waves one of the lengths.  The wait that closes the main
+  // loop covers them like the cell state, so the epilogue starts on LDS reads, not on a global load.
   auto issue_c = [&]() __attribute__((always_inline)) {
     constexpr int RPP = 64 / C::CPR, NPC = C::CPIECES >= NWAVE ? C::CPIECES / NWAVE : 1;
     const int cr = lane / C::CPR, cc = lane % C::CPR;
@@ -305,6 +316,18 @@ __device__ __forceinline__ void lstm_i8_step(const EncStepArgs& a, int mt, int n
       const int p = wave * NPC + pc;
       if (C::CPIECES < NWAVE && p >= C::CPIECES) break;  // wave-uniform
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsC, (lds_void*)(lds + cbuf + p * 1024), 16, vo, RPP * p * H * 2, 0, 0);
+    }
+    if (wave < C::BQ_PIECES) {  // wave-uniform
+      const __amdgpu_buffer_rsrc_t rsQ =
+          __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.bq + m0), (short)0, 0x7ffffff0, 0x00020000);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQ, (lds_void*)(lds + cbuf + C::BQ_OFF + wave * 256), 4, lane * 4,
+                                               wave * 256, 0, 0);
+    } else if (a.mode == ENC_OUT_STACKED && wave < C::BQ_PIECES + C::LENS_PIECES) {
+      const int p = wave - C::BQ_PIECES;
+      const __amdgpu_buffer_rsrc_t rsL =
+          __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(a.lens + n0), (short)0, 0x7ffffff0, 0x00020000);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsL, (lds_void*)(lds + cbuf + C::LENS_OFF + p * 256), 4, lane * 4,
+                                               p * 256, 0, 0);
     }
   };
 
@@ -399,7 +422,7 @@ __device__ __forceinline__ void lstm_i8_step(const EncStepArgs& a, int mt, int n
   EST_PUT(9, est_work);
   EST_PUT(10, (unsigned long long)nS);
 #endif
-  // the cell-state DMA has landed for every wave, all fragment reads are done
+  // the cell-state, bias and length DMA has landed for every wave, all fragment reads are done
   asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #ifdef RNNT_DEV_STAMPS
   EST_PUT(4, __builtin_amdgcn_s_memrealtime());
@@ -411,7 +434,7 @@ __device__ __forceinline__ void lstm_i8_step(const EncStepArgs& a, int mt, int n
   const float2* tab = (const float2*)(smem + C::TAB_OFF);
   float4 bq[WMT];
 #pragma unroll
-  for (int i = 0; i < WMT; ++i) bq[i] = *(const float4*)(a.bq + R + i * 16 + q * 4);
+  for (int i = 0; i < WMT; ++i) bq[i] = *(const float4*)(smem + cbuf + C::BQ_OFF + (R - m0 + i * 16 + q * 4) * 4);
   // results go to LDS first and leave as whole row segments (16 B per lane, full cache lines per
   // wave instruction) instead of scattered per-lane stores: c_new in place over the c_in image
   // (each lane rewrites exactly what it read), h and y / the bf16 output in the other stage
@@ -501,7 +524,8 @@ __device__ __forceinline__ void lstm_i8_step(const EncStepArgs& a, int mt, int n
       // frames t >= x_lens[n] are zeroed; the odd-T pad frame is zero too.
       const size_t dst = (size_t)n * (2 * H) + um + ch * 16;
       uint4 v = *(const uint4*)(ys + r * HP + ch * 16);
-      if (a.t >= a.lens[n]) v = uint4{0u, 0u, 0u, 0u};  // a value select: no pointer select into a stack temporary
+      // the row's length from the staged image; a value select: no pointer select into a stack temporary
+      if (a.t >= *(const int32_t*)(smem + cbuf + C::LENS_OFF + r * 4)) v = uint4{0u, 0u, 0u, 0u};
       st16<WT>(a.y8, dst + a.half * H, v);
       if (a.zero_next) st16<WT>(a.y8, dst + H, uint4{0u, 0u, 0u, 0u});
     }
@@ -570,10 +594,23 @@ __global__ void __launch_bounds__(NWAVE * 64) lstm_i8_tick_kernel(EncTickArgs ar
   extern __shared__ __attribute__((aligned(16))) int8_t smem[];
   unsigned long long st_t0 = 0ull;
   EST_MARK(st_t0);
-  // sigma table into LDS (read after the main loop's first stage barrier)
+  // sigma table into LDS by DMA, 1 KiB pieces dealt to the waves: no VGPR round trip and no wait
+  // here, so the tile pick and the first stages' DMA follow at once.  Every stage's pieces are
+  // younger than the table's and vmcnt retires a wave's loads in issue order, so each wait_stage
+  // (whatever its count) covers this wave's table pieces, and its barrier every wave's; the table
+  // is first read in the epilogue.  The table's bytes stay ahead of stage 0 on the load path: issued
+  // inside the main loop they cost it more than the prologue saves (MEASUREMENTS.md section 12).
+  {
+    typedef __attribute__((address_space(3))) char lds_c;
+    constexpr int TPW = ENC_TAB_N * 8 / (NWAVE * 1024);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    lds_c* tab = (lds_c*)(__attribute__((address_space(3))) void*)smem + C::TAB_OFF;
+    const __amdgpu_buffer_rsrc_t rsT = __builtin_amdgcn_make_buffer_rsrc((void*)g_act_tab, (short)0, 0x7ffffff0, 0x00020000);
 #pragma unroll
-  for (int i = 0; i < ENC_TAB_N / (2 * NWAVE * 64); ++i)
-    ((float4*)(smem + C::TAB_OFF))[i * NWAVE * 64 + threadIdx.x] = ((const float4*)g_act_tab)[i * NWAVE * 64 + threadIdx.x];
+    for (int j = 0; j < TPW; ++j)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsT, (__attribute__((address_space(3))) void*)(tab + (wave * TPW + j) * 1024), 16,
+                                               lane * 16, (wave * TPW + j) * 1024, 0, 0);
+  }
   int mt = 0, nt = 0;
   const int jsel = xcd_pick<C>(args, blockIdx.x & 7, blockIdx.x >> 3, mt, nt);
   if (jsel < 0) return;
